@@ -2,7 +2,8 @@
 """bench.py -- SOR sweeps ("iterations")/s and achieved HBM GB/s on a 3840x2160 flow problem.
 
 Contract (driver):  python bench.py --gpus N --steps K --warmup W   (N>1: launched by
-torch.distributed.run, one rank per GPU).  Prints ONE JSON line on rank 0.
+torch.distributed.run, one rank per GPU).  Prints ONE JSON line on rank 0.  --dump-outputs DIR also writes
+(a fixed sample of) the iterate the last timed step returned, so that two builds can be compared output for output.
 
 Workload (BASELINE.md row "M"/"C4"; BASELINE.json metric): the early-linearization (Horn-Schunck
 type) point solver `Oflow_sor_elin4_2d` / GS_SOR_elin4_2d on one 2160 x 3840 float32 frame
@@ -142,6 +143,22 @@ def host_call(capi, U, V, coef, mode, reps=7):
     return sorted(times)[len(times) // 2] * 1e3, ou, ov
 
 
+DUMP_PIXELS, DUMP_SEED = 1 << 22, 0   # U and V at 4K are 66 MB together, over the 64 MB a dump may hold
+
+
+def dump_outputs(out_dir, planes):
+    """Write DIR/<name>.npy (float32, 1-D) for each [ncols, nrows] plane: the same fixed sample of DUMP_PIXELS pixels of every
+    plane, drawn with numpy's default_rng(DUMP_SEED) without replacement, in ascending flat order (flat index = j * nrows + i,
+    MATLAB's column-major linear index)."""
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    n = next(iter(planes.values())).numel()
+    idx = torch.from_numpy(np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=min(n, DUMP_PIXELS), replace=False)))
+    for name, t in planes.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.reshape(-1)[idx.to(t.device)].float().cpu().numpy())
+
+
 def main():
     # The bench owns the device: the exact-order walkers may take the per-XCD lists (an opt-in because they are live only while
     # the call's whole grid is resident: DESIGN.md 5.2).  Reported in config.knobs; PDEIP_PERSIST_XCD=0 in the environment wins.
@@ -154,7 +171,12 @@ def main():
                     help="solver calls timed for the CPU baseline (0 = skip); 40 calls x 4 sweeps take ~9 s on one core")
     ap.add_argument("--headline-only", action="store_true",
                     help="only the timed red-black workload (what the rocprofv3 summary under profiles/ is taken from)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the iterate the last timed step returned (U, V) to DIR/U.npy, DIR/V.npy: "
+                         "float32, a fixed seeded sample of %d pixels of each plane (see dump_outputs)" % DUMP_PIXELS)
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -267,6 +289,11 @@ def main():
         U, V = state[0]
     if not (bool(torch.isfinite(U).all()) and bool(torch.isfinite(V).all())):
         raise SystemExit("bench.py: the iterate is not finite after the timed loop (the workload must converge)")
+    if args.dump_outputs:
+        fU, fV = dom.gather_owned(U), dom.gather_owned(V)   # N > 1: the whole frame on rank 0
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"U": fU, "V": fV})
+        del fU, fV
     # N > 1: what the slabs hold must be, bit for bit, what ONE domain holds after the same number of red-black sweeps.  Rank 0
     # gathers the owned columns and relaxes the whole frame by the same number of solver calls (outside every timed region).
     parity_slabs = None
