@@ -4,6 +4,9 @@
 Contract (driver):  python bench.py --gpus N --steps K --warmup W   (N>1: launched by
 torch.distributed.run, one rank per GPU).  Prints ONE JSON line on rank 0.  --dump-outputs DIR also writes
 (a fixed sample of) the iterate the last timed step returned, so that two builds can be compared output for output.
+A plain run measures the headline only: `value` (with `value_cold`, `value_repeats` and the `roofline` of the same timed
+launches).  --full adds everything else below (exact_order, parity_rb, host_call, cpu_baseline and the other solvers, levels,
+drivers and configs at N = 1; parity_slabs at N > 1), all of it after the timed steps and the dump.
 
 Workload (BASELINE.md row "M"/"C4"; BASELINE.json metric): the early-linearization (Horn-Schunck
 type) point solver `Oflow_sor_elin4_2d` / GS_SOR_elin4_2d on one 2160 x 3840 float32 frame
@@ -167,10 +170,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check everything else: exact order, CPU baselines and parity, "
+                         "host-pointer calls, the other solvers, levels, drivers and configs (N = 1), the slab self-check (N > 1)")
     ap.add_argument("--cpu-calls", type=int, default=40,
-                    help="solver calls timed for the CPU baseline (0 = skip); 40 calls x 4 sweeps take ~9 s on one core")
-    ap.add_argument("--headline-only", action="store_true",
-                    help="only the timed red-black workload (what the rocprofv3 summary under profiles/ is taken from)")
+                    help="with --full: solver calls timed for the CPU baseline (0 = skip); 40 calls x 4 sweeps take ~9 s on one core")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="after the timed steps, write the iterate the last timed step returned (U, V) to DIR/U.npy, DIR/V.npy: "
                          "float32, a fixed seeded sample of %d pixels of each plane (see dump_outputs)" % DUMP_PIXELS)
@@ -297,7 +301,7 @@ def main():
     # N > 1: what the slabs hold must be, bit for bit, what ONE domain holds after the same number of red-black sweeps.  Rank 0
     # gathers the owned columns and relaxes the whole frame by the same number of solver calls (outside every timed region).
     parity_slabs = None
-    if world > 1:
+    if world > 1 and args.full:
         gU, gV = dom.gather_owned(U), dom.gather_owned(V)
         if rank == 0:
             a, b2 = (U0.clone(), V0.clone()), (torch.empty_like(U0), torch.empty_like(V0))
@@ -370,7 +374,7 @@ def main():
         except (ValueError, OSError):
             pass
 
-    if world == 1 and not args.headline_only:
+    if world == 1 and args.full:
         # ---- exact (reference) ordering on the same workload -------------------------------------
         Ue, Ve = U0.clone(), V0.clone()
 
