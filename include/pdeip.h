@@ -543,6 +543,46 @@ int pdeip_flow_nd_llin(const float *Iin, int nrows, int ncols, int channels, int
 int pdeip_disp_nd_llin(const float *Il, const float *Ir, int nrows, int ncols, int channels, int fst_term, int snd_term,
                        const pdeip_driver_params *prm, const double *Us, float *U);
 
+/* ---- level sets: the active-contour section of runme.m (csrc/pdeip_levelset.hip) ------------------------------------------
+ * Arrays as everywhere: column-major float32 [nrows x ncols x nframes]; frames are planes solved independently.  nrows, ncols
+ * >= 2 (PDEIP_ERR_ARG otherwise, before any HIP call); lines of any length (the reference stops at MAX_BUF_SIZE = 2048).
+ * AOS has one order: pdeip_set_mode does not apply.  PHI_out must not alias an input.
+ *
+ * PHI_out = AC_solver_2d(PHI, D, GradNorm, Diff, tau, nu) (mex/source/AC_solver_2d.c -> AC_AOS_4_2d, levelsetSolvers.c:145-181):
+ * one AOS step of the geodesic active contour -- a Thomas solve along every column, one along every row, their sum with both
+ * passes' Diff == 0 rules, then one re-initialisation step (T = 0.25).  Bit-identical to the reference's column and row passes;
+ * the re-initialisation step follows the sign-function contract below. */
+int pdeip_ac_solver(const float *PHI, const float *D, const float *GradNorm, const float *Diff, int nrows, int ncols, int nframes,
+                    float tau, float nu, float *PHI_out);
+/* PHI_out = Reinit(PHI, T) (mex/source/Reinit.c -> reinit, levelsetSolvers.c:969-1118): as many re-initialisation steps as the
+ * reference's loop for (t = 0; t < T; t += 0.25f) runs (T <= 0 or NaN: none, PHI_out = PHI; a T at which t stops growing is
+ * refused).  Unlike the reference gateway, PHI is not modified.  Sign-function contract: the reference's SSE path uses
+ * rsqrtps (a 12-bit estimate); this library computes S = PHI * (1.0f / sqrtf(PHI*PHI + sqrtf((PHIx*PHIx + PHIy*PHIy) +
+ * FLT_EPSILON))) with correctly rounded sqrtf and division -- the same operation order, not bit-identical at that step. */
+int pdeip_reinit(const float *PHI, int nrows, int ncols, int nframes, float T, float *PHI_out);
+/* Device-pointer forms of the two, asynchronous on `stream`; workspace from the library's cache. */
+int pdeip_ac_solver_dev(void *stream, const float *PHI, const float *D, const float *GradNorm, const float *Diff, int nrows,
+                        int ncols, int nframes, float tau, float nu, float *PHI_out);
+int pdeip_reinit_dev(void *stream, const float *PHI, int nrows, int ncols, int nframes, float T, float *PHI_out);
+/* PHIout = GAC_v10a(Iin, PHIin, param) / GAC_v10b(Iin, PHIin, param) (matlab/active_contour/GAC_v10a.m, GAC_v10b.m; runme.m:128-131):
+ * the whole geodesic-active-contour driver in one call, resident on the device.  Iin: single [nrows x ncols x channels] (runme.m
+ * divides by 255); PHIin: single [nrows x ncols]; PHIout: [nrows x ncols]; nrows, ncols >= 3.  model: PDEIP_GAC_A (balloon
+ * force c, upwind gradient) or PDEIP_GAC_B (convection along grad g, circshift wrapping at the borders).  Reinit(PHIin, 10),
+ * the 7x7 Gaussian (sigma 2.5) and the [-1 0 1]*0.5 derivatives are this library's definitions of the IPT calls (pyramid.py);
+ * lambda < 0 selects sort(Igrad(:))(round(0.7*N)) on the device.  Every member of the parameter struct that is NaN keeps the
+ * driver's default (tau 0.25, c -0.1 (model a only), lambda -1 = automatic, iter = ITER 100, smooth = SMOOTH 100): a NaN, not
+ * <= 0, because c is negative by default and a negative lambda means "automatic".  NULL: all defaults. */
+#define PDEIP_GAC_A 0
+#define PDEIP_GAC_B 1
+typedef struct pdeip_gac_params {
+    double tau, c, lambda, iter, smooth;
+} pdeip_gac_params;
+int pdeip_gac(const float *Iin, int nrows, int ncols, int channels, const float *PHIin, int model, const pdeip_gac_params *prm,
+              float *PHIout);
+/* The same on device pointers, asynchronous on `stream` (no host read-back inside: graph-capturable). */
+int pdeip_gac_dev(void *stream, const float *Iin, int nrows, int ncols, int channels, const float *PHIin, int model,
+                  const pdeip_gac_params *prm, float *PHIout);
+
 #ifdef __cplusplus
 }
 #endif

@@ -118,6 +118,13 @@ SIGNATURES = {
     "pdeip_flow_fas_fmg_elin": [_P, _I, _I, _I, _P, _P, _P],
     "pdeip_tvdenoise8": [_P, _I, _I, _I, _P, _P],
     "pdeip_tvdenoise4": [_P, _I, _I, _I, _P, _P],
+    # level sets (csrc/pdeip_levelset.hip)
+    "pdeip_ac_solver": [_P, _P, _P, _P, _I, _I, _I, _F, _F, _P],
+    "pdeip_reinit": [_P, _I, _I, _I, _F, _P],
+    "pdeip_ac_solver_dev": [_P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P],
+    "pdeip_reinit_dev": [_P, _P, _I, _I, _I, _F, _P],
+    "pdeip_gac": [_P, _I, _I, _I, _P, _I, _P, _P],
+    "pdeip_gac_dev": [_P, _P, _I, _I, _I, _P, _I, _P, _P],
     # library state
     "pdeip_set_mode": [_I],
     "pdeip_get_mode": [],

@@ -20,7 +20,7 @@
 
 namespace pdeip {
 
-enum { WS_AUX0 = 0, WS_AUX1, WS_PING, WS_ARENA, WS_CTL, WS_ORDER, WS_ALR, WS_ALR_T, WS_TV, WS_SMALL, WS_MAIL, WS_PACK, WS_DRIVER, WS_LEX, WS_NSLOT };
+enum { WS_AUX0 = 0, WS_AUX1, WS_PING, WS_ARENA, WS_CTL, WS_ORDER, WS_ALR, WS_ALR_T, WS_TV, WS_SMALL, WS_MAIL, WS_PACK, WS_DRIVER, WS_LEX, WS_LS, WS_NSLOT };
 
 constexpr int MAX_DEVICES = 16;
 
@@ -127,6 +127,9 @@ inline dim3 pixel_grid(int nrows, int ncols, int nz) { return dim3((unsigned)((n
 int use_device();
 int use_device(int device);
 void read_env_once();
+
+// fspecial('gaussian', [size size], sigma) / its sum, as pyramid.py states it (row-major doubles; pdeip_drivers.hip).
+std::vector<double> gaussian_mask(int size, double sigma);
 
 // ---- host staging (pdeip_host.hip) ---------------------------------------------------------------------
 inline size_t pad4(size_t n) { return (n + 3) & ~(size_t)3; }

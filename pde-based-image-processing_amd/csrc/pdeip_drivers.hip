@@ -98,6 +98,9 @@ Params merge(const pdeip_driver_params *u, const Params &d)
     return p;
 }
 
+} // namespace
+
+namespace pdeip {
 // fspecial('gaussian', [size size], sigma) as pyramid.py states it (row-major doubles), before the division by the sum
 std::vector<double> gaussian(int size, double sigma)
 {
@@ -134,6 +137,10 @@ std::vector<double> gaussian_mask(int size, double sigma)
     for (double &v : g) v /= s;
     return g;
 }
+
+} // namespace pdeip
+
+namespace {
 
 // imresize(A, [out_rows out_cols], 'bilinear') of a DOUBLE array on the host, as pyramid.resize(..., out_dtype=float64) does it:
 // triangle kernel at MATLAB's pixel-centre convention, stretched by 1/scale when shrinking, taps normalised, rows first, then

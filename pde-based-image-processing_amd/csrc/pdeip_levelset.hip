@@ -1,0 +1,262 @@
+// pdeip_levelset.hip -- libpdeip.so: the level-set gateways of the active-contour section of runme.m.
+//
+//   PHI_out = AC_solver_2d(PHI, D, GradNorm, Diff, tau, nu)   mex/source/AC_solver_2d.c -> AC_AOS_4_2d   pdeip_ac_solver(_dev)
+//   PHI_out = Reinit(PHI, T)                                  mex/source/Reinit.c       -> reinit         pdeip_reinit(_dev)
+//
+// Kernels: csrc/pdeip_levelset.hpp.  AOS has one order, so pdeip_set_mode does not apply.  Multi-frame inputs are planes
+// solved independently, as in the reference.  Lines of any length are accepted (the reference stops at MAX_BUF_SIZE = 2048).
+//
+// Build (build.py): hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -c, one object per translation unit.
+#include "pdeip_ctx.hpp"
+#include "pdeip_levelset.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <utility>
+#include <vector>
+
+using namespace pdeip;
+using namespace pdeip::ls;
+
+namespace {
+
+// nrows, ncols >= 2: at 1 the reference reads outside the line (undefined behaviour), so it is refused before any HIP call.
+int check_ls_dims(const char *who, int nrows, int ncols, int nframes)
+{
+    if (nrows < 2 || ncols < 2)
+        return set_err(PDEIP_ERR_ARG, "%s: PHI must be at least 2x2 (got %dx%d)", who, nrows, ncols);
+    if (nframes < 1) return set_err(PDEIP_ERR_ARG, "%s: number of frames must be >= 1 (got %d)", who, nframes);
+    if ((long long)nrows * ncols * nframes > 0x7fffffffLL) return set_err(PDEIP_ERR_ARG, "%s: more than 2^31-1 elements", who);
+    return PDEIP_OK;
+}
+
+// Steps of the reference's loop `for (t = 0.0f; t < T; t += 0.25f)` (levelsetSolvers.c:1076): T <= 0 or NaN gives none.
+// Where t + 0.25f no longer changes t the reference never ends; that T is refused.
+int reinit_step_count(const char *who, float T, int *steps)
+{
+    int n = 0;
+    for (float t = 0.0f; t < T; t += 0.25f) {
+        if (t + 0.25f == t || n == 0x7fffffff) return set_err(PDEIP_ERR_ARG, "%s: T = %g never ends the reference's time loop", who, (double)T);
+        n++;
+    }
+    *steps = n;
+    return PDEIP_OK;
+}
+
+int launch_reinit_step(hipStream_t s, const float *in, float *out, int nrows, int ncols, int nframes)
+{
+    hipLaunchKernelGGL(k_reinit_step, pixel_grid(nrows, ncols, nframes), dim3(256), 0, s, in, out, nrows, ncols);
+    HIPCHK(hipGetLastError());
+    tls.last_launches++;
+    return PDEIP_OK;
+}
+
+int upload(float *dst, const float *src, size_t n)
+{
+    HIPCHK(hipMemcpy(dst, src, n * sizeof(float), hipMemcpyHostToDevice));
+    return PDEIP_OK;
+}
+
+} // namespace
+
+extern "C" int pdeip_ac_solver_dev(void *stream, const float *PHI, const float *D, const float *GradNorm, const float *Diff,
+                                   int nrows, int ncols, int nframes, float tau, float nu, float *PHI_out)
+{
+    const char *who = "pdeip_ac_solver_dev";
+    NONNULL(who, PHI); NONNULL(who, D); NONNULL(who, GradNorm); NONNULL(who, Diff); NONNULL(who, PHI_out);
+    RC(check_ls_dims(who, nrows, ncols, nframes));
+    if (PHI_out == PHI || PHI_out == D || PHI_out == GradNorm || PHI_out == Diff)
+        return set_err(PDEIP_ERR_ARG, "%s: PHI_out must not alias an input", who);
+    tls.last_launches = 0;
+    const size_t nf = (size_t)nrows * ncols * nframes;
+    float *ws = nullptr;
+    RC(ws_get(WS_LS, pad4(nf) * 3 * sizeof(float), &ws));
+    float *cp = ws, *dp = ws + pad4(nf), *sum = ws + 2 * pad4(nf);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // column pass -> PHI_out (AC_TDMA_column4), row pass -> sum (AC_TDMA_row4), one re-initialisation step -> PHI_out (:178)
+    hipLaunchKernelGGL(k_aos_col, dim3((unsigned)((ncols + LS_BLOCK - 1) / LS_BLOCK), (unsigned)nframes), dim3(LS_BLOCK), 0, s,
+                       PHI, D, GradNorm, Diff, PHI_out, cp, dp, nrows, ncols, tau, nu);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_aos_row, dim3((unsigned)((nrows + LS_BLOCK - 1) / LS_BLOCK), (unsigned)nframes), dim3(LS_BLOCK), 0, s,
+                       PHI, D, GradNorm, Diff, PHI_out, sum, cp, dp, nrows, ncols, tau, nu);
+    HIPCHK(hipGetLastError());
+    tls.last_launches += 2;
+    return launch_reinit_step(s, sum, PHI_out, nrows, ncols, nframes);
+}
+
+extern "C" int pdeip_reinit_dev(void *stream, const float *PHI, int nrows, int ncols, int nframes, float T, float *PHI_out)
+{
+    const char *who = "pdeip_reinit_dev";
+    NONNULL(who, PHI); NONNULL(who, PHI_out);
+    RC(check_ls_dims(who, nrows, ncols, nframes));
+    if (PHI_out == PHI) return set_err(PDEIP_ERR_ARG, "%s: PHI_out must not alias PHI", who);
+    int steps = 0;
+    RC(reinit_step_count(who, T, &steps));
+    tls.last_launches = 0;
+    const size_t nf = (size_t)nrows * ncols * nframes;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (steps == 0) return copy_d2d(s, PHI_out, PHI, nf);
+    float *scr = nullptr;
+    if (steps > 1) RC(ws_get(WS_LS, pad4(nf) * sizeof(float), &scr));
+    // ping-pong so that the last step lands in PHI_out; PHI itself is never written
+    const float *src = PHI;
+    for (int k = 0; k < steps; k++) {
+        float *dst = ((steps - k) & 1) ? PHI_out : scr;
+        RC(launch_reinit_step(s, src, dst, nrows, ncols, nframes));
+        src = dst;
+    }
+    return PDEIP_OK;
+}
+
+extern "C" int pdeip_ac_solver(const float *PHI, const float *D, const float *GradNorm, const float *Diff, int nrows, int ncols,
+                               int nframes, float tau, float nu, float *PHI_out)
+{
+    const char *who = "AC_solver_2D";
+    NONNULL(who, PHI); NONNULL(who, D); NONNULL(who, GradNorm); NONNULL(who, Diff); NONNULL(who, PHI_out);
+    RC(check_ls_dims(who, nrows, ncols, nframes));
+    RC(use_device());
+    const size_t nf = (size_t)nrows * ncols * nframes, p = pad4(nf);
+    float *ar = nullptr;
+    RC(ws_get(WS_ARENA, p * 5 * sizeof(float), &ar));
+    float *dP = ar, *dD = ar + p, *dG = ar + 2 * p, *dF = ar + 3 * p, *dO = ar + 4 * p;
+    RC(upload(dP, PHI, nf)); RC(upload(dD, D, nf)); RC(upload(dG, GradNorm, nf)); RC(upload(dF, Diff, nf));
+    RC(pdeip_ac_solver_dev(nullptr, dP, dD, dG, dF, nrows, ncols, nframes, tau, nu, dO));
+    HIPCHK(hipMemcpy(PHI_out, dO, nf * sizeof(float), hipMemcpyDeviceToHost));
+    return PDEIP_OK;
+}
+
+// Unlike Reinit.c:136-137, which re-initialises its input array in place before copying it out, PHI is left as it was.
+extern "C" int pdeip_reinit(const float *PHI, int nrows, int ncols, int nframes, float T, float *PHI_out)
+{
+    const char *who = "reInitC";
+    NONNULL(who, PHI); NONNULL(who, PHI_out);
+    RC(check_ls_dims(who, nrows, ncols, nframes));
+    int steps = 0;
+    RC(reinit_step_count(who, T, &steps));
+    const size_t nf = (size_t)nrows * ncols * nframes, p = pad4(nf);
+    if (steps == 0) { // nothing to compute: the output is the input
+        if (PHI_out != PHI) memcpy(PHI_out, PHI, nf * sizeof(float));
+        return PDEIP_OK;
+    }
+    RC(use_device());
+    float *ar = nullptr;
+    RC(ws_get(WS_ARENA, p * 2 * sizeof(float), &ar));
+    float *dP = ar, *dO = ar + p;
+    RC(upload(dP, PHI, nf));
+    RC(pdeip_reinit_dev(nullptr, dP, nrows, ncols, nframes, T, dO));
+    HIPCHK(hipMemcpy(PHI_out, dO, nf * sizeof(float), hipMemcpyDeviceToHost));
+    return PDEIP_OK;
+}
+
+// ---- PHIout = GAC_v10a(Iin, PHIin, ...) / GAC_v10b(...): the whole driver, resident ------------------------------------------
+// matlab/active_contour/GAC_v10a.m:35-121 and GAC_v10b.m.  Reinit(PHIin, 10); imfilter(Iin, fspecial('gaussian',[7 7],2.5),
+// 'replicate') per channel and the [-1 0 1]*0.5 derivatives as pyramid.py defines those IPT calls; the largest derivative over
+// the channels; lambda = sort(Igrad(:))(round(0.7*N)) selected on the device when param.lambda < 0; g; then `while iter < ITER`
+// the model's data term and one AC_solver_2d step.  Nothing is read back to the host inside the run.
+namespace {
+
+struct GacPrm {
+    double tau, c, lambda, iter, smooth;
+};
+GacPrm gac_resolve(const pdeip_gac_params *u)
+{
+    GacPrm p{0.25, -0.1, -1.0, 100.0, 100.0}; // GAC_v10a.m:35-42
+    if (u) {
+        if (!std::isnan(u->tau)) p.tau = u->tau;
+        if (!std::isnan(u->c)) p.c = u->c;
+        if (!std::isnan(u->lambda)) p.lambda = u->lambda;
+        if (!std::isnan(u->iter)) p.iter = u->iter;
+        if (!std::isnan(u->smooth)) p.smooth = u->smooth;
+    }
+    return p;
+}
+
+} // namespace
+
+extern "C" int pdeip_gac_dev(void *stream, const float *Iin, int nrows, int ncols, int channels, const float *PHIin, int model,
+                             const pdeip_gac_params *prm, float *PHIout)
+{
+    const char *who = "pdeip_gac_dev";
+    NONNULL(who, Iin); NONNULL(who, PHIin); NONNULL(who, PHIout);
+    if (nrows < 3 || ncols < 3) return set_err(PDEIP_ERR_ARG, "%s: image must be at least 3x3 (got %dx%d)", who, nrows, ncols);
+    if (channels < 1) return set_err(PDEIP_ERR_ARG, "%s: number of channels must be >= 1 (got %d)", who, channels);
+    if ((long long)nrows * ncols * (channels + 9) > 0x7fffffffLL) return set_err(PDEIP_ERR_ARG, "%s: image too large", who);
+    if (model != PDEIP_GAC_A && model != PDEIP_GAC_B) return set_err(PDEIP_ERR_ARG, "%s: model must be PDEIP_GAC_A or PDEIP_GAC_B", who);
+    const GacPrm p = gac_resolve(prm);
+    if (!(p.iter < 2147483647.0)) return set_err(PDEIP_ERR_ARG, "%s: ITER = %g is too large", who, p.iter);
+    const int iters = p.iter > 0.0 ? (int)std::ceil(p.iter) : 0; // iterations of `iter = 0; while iter < ITER`
+    const size_t n = (size_t)nrows * ncols, pn = pad4(n);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+
+    float *ws = nullptr;
+    const size_t sel_floats = (sizeof(Select) + 3) / 4 + 8; // lambda (4 floats, keeps the state 16-byte aligned) + the state
+    RC(ws_get(WS_DRIVER, (pn * ((size_t)channels + 9) + sel_floats) * sizeof(float), &ws));
+    float *Ism = ws, *Igrad = Ism + pn * channels, *g = Igrad + pn, *gdx = g + pn, *gdy = gdx + pn, *P0 = gdy + pn, *P1 = P0 + pn;
+    float *DATA = P1 + pn, *gradPHI = DATA + pn, *Diff = gradPHI + pn, *lam = Diff + pn;
+    Select *sel = reinterpret_cast<Select *>(lam + 4);
+    int launches = 0;
+
+    RC(pdeip_reinit_dev(s, PHIin, nrows, ncols, 1, 10.0f, P0)); // Reinit(single(PHIin), single(10)): 40 steps
+    launches += tls.last_launches;
+    const std::vector<double> G = gaussian_mask(7, 2.5);
+    RC(pdeip_pyr_smooth_dev(s, Iin, nrows, ncols, channels, G.data(), 7, Ism));
+    const dim3 grid = pixel_grid(nrows, ncols, 1), blk(256);
+    hipLaunchKernelGGL(k_gac_igrad, grid, blk, 0, s, Ism, Igrad, nrows, ncols, channels);
+    HIPCHK(hipGetLastError());
+    launches += 2;
+    const float *lam_dev = nullptr;
+    if (p.lambda < 0.0) {
+        const double kd = std::round(0.7 * (double)n); // MATLAB round: half away from zero; 1-based rank
+        const unsigned k = kd < 1.0 ? 1u : (unsigned)kd;
+        hipLaunchKernelGGL(k_sel_init, dim3(1), dim3(256), 0, s, sel, k);
+        const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 1024);
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            hipLaunchKernelGGL(k_sel_hist, dim3(blocks), dim3(256), 0, s, sel, Igrad, n, shift);
+            hipLaunchKernelGGL(k_sel_pick, dim3(1), dim3(64), 0, s, sel, shift, lam);
+        }
+        HIPCHK(hipGetLastError());
+        launches += 9;
+        lam_dev = lam;
+    }
+    hipLaunchKernelGGL(k_gac_g, dim3((unsigned)((n + 255) / 256)), blk, 0, s, Igrad, g, n, lam_dev, (float)p.lambda);
+    launches++;
+    if (model == PDEIP_GAC_B) {
+        hipLaunchKernelGGL(k_gac_gd, grid, blk, 0, s, g, gdx, gdy, nrows, ncols);
+        launches++;
+    }
+    HIPCHK(hipGetLastError());
+    float *cur = P0, *nxt = P1;
+    for (int it = 0; it < iters; it++) {
+        if (model == PDEIP_GAC_A)
+            hipLaunchKernelGGL(k_gac_terms<0>, grid, blk, 0, s, cur, g, gdx, gdy, (float)p.c, p.c <= 0.0 ? 1 : 0, DATA, gradPHI, Diff, nrows, ncols);
+        else
+            hipLaunchKernelGGL(k_gac_terms<1>, grid, blk, 0, s, cur, g, gdx, gdy, (float)p.c, 0, DATA, gradPHI, Diff, nrows, ncols);
+        HIPCHK(hipGetLastError());
+        RC(pdeip_ac_solver_dev(s, cur, DATA, gradPHI, Diff, nrows, ncols, 1, (float)p.tau, (float)p.smooth, nxt));
+        launches += 1 + tls.last_launches;
+        std::swap(cur, nxt);
+    }
+    RC(copy_d2d(s, PHIout, cur, n));
+    tls.last_launches = launches + 1;
+    return PDEIP_OK;
+}
+
+extern "C" int pdeip_gac(const float *Iin, int nrows, int ncols, int channels, const float *PHIin, int model,
+                         const pdeip_gac_params *prm, float *PHIout)
+{
+    const char *who = "pdeip_gac";
+    NONNULL(who, Iin); NONNULL(who, PHIin); NONNULL(who, PHIout);
+    if (nrows < 3 || ncols < 3) return set_err(PDEIP_ERR_ARG, "%s: image must be at least 3x3 (got %dx%d)", who, nrows, ncols);
+    if (channels < 1) return set_err(PDEIP_ERR_ARG, "%s: number of channels must be >= 1 (got %d)", who, channels);
+    if (model != PDEIP_GAC_A && model != PDEIP_GAC_B) return set_err(PDEIP_ERR_ARG, "%s: model must be PDEIP_GAC_A or PDEIP_GAC_B", who);
+    RC(use_device());
+    const size_t n = (size_t)nrows * ncols, p = pad4(n);
+    float *ar = nullptr;
+    RC(ws_get(WS_ARENA, p * ((size_t)channels + 2) * sizeof(float), &ar));
+    float *dI = ar, *dP = ar + p * channels, *dO = dP + p;
+    RC(upload(dI, Iin, n * channels));
+    RC(upload(dP, PHIin, n));
+    RC(pdeip_gac_dev(nullptr, dI, nrows, ncols, channels, dP, model, prm, dO));
+    HIPCHK(hipMemcpy(PHIout, dO, n * sizeof(float), hipMemcpyDeviceToHost));
+    return PDEIP_OK;
+}

@@ -192,6 +192,20 @@ def warp_bilinear(Iin, X, Y, Iout):
     capi.call("pdeip_warp_bilinear_dev", _stream(), *_p(Iin, X, Y), nrows, ncols, F, Iout.data_ptr())
 
 
+def ac_solver(PHI, D, GradNorm, Diff, tau, nu, out):
+    """out = one AOS step of the geodesic active contour (AC_solver_2d); `out` must not alias an input."""
+    _chk(PHI, D, GradNorm, Diff, out)
+    nrows, ncols, F = _dims(PHI)
+    capi.call("pdeip_ac_solver_dev", _stream(), *_p(PHI, D, GradNorm, Diff), nrows, ncols, F, float(tau), float(nu), out.data_ptr())
+
+
+def reinit(PHI, T, out):
+    """out = Reinit(PHI, T): the re-initialisation steps of t = 0:0.25:T (PHI is not modified)."""
+    _chk(PHI, out)
+    nrows, ncols, F = _dims(PHI)
+    capi.call("pdeip_reinit_dev", _stream(), PHI.data_ptr(), nrows, ncols, F, float(T), out.data_ptr())
+
+
 def fst_derivatives5(It0, It1, Idt, Idx, Idy):
     _chk(It0, It1, Idt, Idx, Idy)
     nrows, ncols, F = _dims(It0)

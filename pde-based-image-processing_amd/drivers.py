@@ -12,6 +12,7 @@ capi.MODE_RED_BLACK the parallel one).
     DispEminND_llin_2D          matlab/disparity/DispEminND_llin_2D.m             stereo disparity
     DispEminND_llin_sym_2D      matlab/disparity/DispEminND_llin_sym_2D.m         symmetric stereo
     TVdenoise8 / TVdenoise4     matlab/denoising/TVdenoise{8,4}.m                 total-variation denoising
+    GAC_v10a / GAC_v10b         matlab/active_contour/GAC_v10{a,b}.m              geodesic active contours (C++ only: pdeip_gac)
 
 `Us=`, `Vs=` (param.Us / param.Vs: spatial a-priori fields, double, NaN = no constraint) and `scales=` (param.scales) are taken
 by the late-linearisation flow drivers and the disparity driver as the reference's drivers take them.
@@ -441,3 +442,42 @@ def capi_FlowEminNDFASFMG_elin_2D_v10(Iin, channels, mode=capi.MODE_EXACT_ORDER,
     finally:
         capi.set_mode(old)
     return U, V
+
+
+class _GacParams(__import__("ctypes").Structure):
+    _fields_ = [(k, __import__("ctypes").c_double) for k in ("tau", "c", "lambda_", "iter", "smooth")]
+
+
+_GAC_KEYS = {"tau": "tau", "c": "c", "lambda": "lambda_", "lambda_": "lambda_", "ITER": "iter", "SMOOTH": "smooth"}
+
+
+def _gac(Iin, PHIin, model, param):
+    import ctypes
+
+    prm = _GacParams(*([float("nan")] * 5))  # NaN: the driver's default
+    for k, v in param.items():
+        if k not in _GAC_KEYS or (model == 1 and k == "c"):
+            raise TypeError("GAC_v10%s: unknown parameter %r" % ("ab"[model], k))
+        setattr(prm, _GAC_KEYS[k], float(v))
+    I = np.asfortranarray(np.asarray(Iin, dtype=np.float32))
+    P = np.asfortranarray(np.asarray(PHIin, dtype=np.float32))
+    rows, cols = I.shape[:2]
+    if P.shape != (rows, cols):
+        raise ValueError("PHIin is %s but the image is %s" % (P.shape, (rows, cols)))
+    out = np.zeros((rows, cols), np.float32, order="F")
+    capi.call("pdeip_gac", I.ctypes.data, rows, cols, I.shape[2] if I.ndim == 3 else 1, P.ctypes.data, model,
+              ctypes.addressof(prm), out.ctypes.data)
+    return out
+
+
+def GAC_v10a(Iin, PHIin, **param):
+    """PHIout = GAC_v10a(Iin, PHIin, ...) (matlab/active_contour/GAC_v10a.m): geodesic active contour with a balloon force, the
+    whole run in one pdeip_gac call.  Iin single [rows, cols(, C)] (runme.m divides by 255); param: tau, c, lambda (pass it as
+    **{"lambda": v} or lambda_=v; < 0: automatic), ITER, SMOOTH, as the driver names them."""
+    return _gac(Iin, PHIin, 0, param)
+
+
+def GAC_v10b(Iin, PHIin, **param):
+    """PHIout = GAC_v10b(Iin, PHIin, ...) (matlab/active_contour/GAC_v10b.m): geodesic active contour with the convection term
+    grad(g) . grad(PHI); parameters as GAC_v10a without c."""
+    return _gac(Iin, PHIin, 1, param)

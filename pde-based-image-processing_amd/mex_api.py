@@ -11,7 +11,7 @@ All arithmetic happens in libpdeip.so on the GPU; this file only checks, packs a
 
 Reference: Oflow_sor_elin4_2d.c, Oflow_sor_llin4_2d.c, Oflow_sor_llin8_2d.c, Oflow_lhs_elin4_2d.c,
 Oflow_lhs_llin4_2d.c, Disp_sor_llin4_2d.c, PDEsolver4.c, PDEsolver8.c, DdiffWeights.c,
-BilinInterp_2d.c, FstDerivatives5.c, SndDerivatives5.c (all under mex/source/).
+BilinInterp_2d.c, FstDerivatives5.c, SndDerivatives5.c, AC_solver_2d.c, Reinit.c (all under mex/source/).
 """
 import numpy as np
 
@@ -257,6 +257,34 @@ def SndDerivatives5(It0, It1, nargout=5):
     """[Idxt,Idyt,Idxx,Idyy,Idxy] = SndDerivatives5(It0,It1)  -- mex/source/SndDerivatives5.c:51-174."""
     return _derivatives("sndDerivatives", "pdeip_snd_derivatives5", It0, It1, 5, nargout,
                         "sndDerivatives: insufficient number of outputs.")
+
+
+def AC_solver_2d(PHI, D, GradNorm, Diff, tau, nu, nargout=1):
+    """PHI_out = AC_solver_2d(PHI_in,D_in,GradNorm_in,Diff_in,tau,nu)  -- mex/source/AC_solver_2d.c:47-228."""
+    who = "AC_solver_2D error"
+    planes = [_single(n, who, a) for n, a in (("PHI_in", PHI), ("D_in", D), ("GradNorm_in", GradNorm), ("Diff_in", Diff))]
+    tau, nu = _scalar("tau", who, tau), _scalar("nu", who, nu)
+    if nargout < 1:
+        raise MexError(capi.PDEIP_ERR_ARG, "ac_solver_2D error insufficient number of outputs. Outputs from this function is 'PHI_out'")
+    PHI = planes[0]
+    if any(a.size != PHI.size for a in planes[1:]):  # the rule and message of mex/levelset/AC_solver_2d.c
+        raise MexError(capi.PDEIP_ERR_ARG, "AC_solver_2D error: 'D_in', 'GradNorm_in' and 'Diff_in' must have the size of 'PHI_in'.")
+    out = _out_like(PHI)
+    nrows, ncols = PHI.shape[:2]
+    _run("pdeip_ac_solver", *[_ptr(a) for a in planes], nrows, ncols, _frames(PHI), tau, nu, _ptr(out))
+    return out
+
+
+def Reinit(PHI, T, nargout=1):
+    """PHI_out = Reinit(PHI_in,T)  -- mex/source/Reinit.c:47-139.  Unlike the reference gateway, PHI_in is left unchanged."""
+    PHI = _single("PHI_in", "reInitC", PHI)
+    T = _scalar("T", "reInitC error", T)
+    if nargout < 1:
+        raise MexError(capi.PDEIP_ERR_ARG, "reInitC error insufficient number of outputs. Outputs from this function is 'PHI_out'")
+    out = _out_like(PHI)
+    nrows, ncols = PHI.shape[:2]
+    _run("pdeip_reinit", _ptr(PHI), nrows, ncols, _frames(PHI), T, _ptr(out))
+    return out
 
 
 def set_mode(mode):

@@ -1,0 +1,303 @@
+"""CPU: the level-set gateways (AC_solver_2d, Reinit) at the boundary, and the numpy restatement's maths on its own.
+
+The restatement (levelset_ref.py) is what the GPU tests compare with bit for bit, so its equations are checked here
+against things it does not share code with: numpy.linalg.solve of the same tridiagonal systems, and the eikonal property a
+re-initialisation must reach."""
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import levelset_ref as ref
+from test_capi_symbols import declared_symbols
+from test_mex_stubs import MOCK_DIR, ROOT, call
+
+LS_DIR = os.path.join(ROOT, "pde-based-image-processing_amd", "mex", "levelset")
+BUILD_DIR = os.path.join(MOCK_DIR, "_build")
+LS_STUBS = ["AC_solver_2d", "Reinit", "GAC_v10a_gpu", "GAC_v10b_gpu"]
+ENTRIES = ["pdeip_ac_solver", "pdeip_ac_solver_dev", "pdeip_reinit", "pdeip_reinit_dev", "pdeip_gac", "pdeip_gac_dev"]
+
+
+def build_ls_stub(name, pdeip):
+    """Compile mex/levelset/<name>.c against the mock MEX runtime (tests/mexmock) and libpdeip.so."""
+    os.makedirs(BUILD_DIR, exist_ok=True)
+    so = os.path.join(BUILD_DIR, "levelset_" + name + ".so")
+    srcs = [os.path.join(LS_DIR, name + ".c"), os.path.join(MOCK_DIR, "mexmock.c")]
+    deps = srcs + [os.path.join(LS_DIR, "..", "pdeip_mex_util.h"), os.path.join(LS_DIR, "pdeip_gac_mex.h"), os.path.join(MOCK_DIR, "mex.h"),
+                   pdeip.capi.LIB_PATH]
+    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
+        libdir = os.path.dirname(pdeip.capi.LIB_PATH)
+        subprocess.run(["gcc", "-O1", "-Wall", "-Wextra", "-Werror", "-Wno-unused-function", "-shared", "-fPIC", "-I" + MOCK_DIR,
+                        "-I" + os.path.join(ROOT, "include"), "-o", so] + srcs + ["-L" + libdir, "-lpdeip", "-Wl,-rpath," + libdir],
+                       check=True)
+    lib = ctypes.CDLL(so)
+    lib.mock_make.restype = ctypes.c_void_p
+    lib.mock_make.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_long), ctypes.c_int, ctypes.c_void_p]
+    lib.mock_free.argtypes = [ctypes.c_void_p]
+    lib.mock_data.restype = ctypes.c_void_p
+    lib.mock_data.argtypes = [ctypes.c_void_p]
+    lib.mock_ndim.argtypes = [ctypes.c_void_p]
+    lib.mock_dim.restype = ctypes.c_long
+    lib.mock_dim.argtypes = [ctypes.c_void_p, ctypes.c_int]
+    lib.mock_last_error.restype = ctypes.c_char_p
+    lib.mock_call.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
+    return lib
+
+
+# ---- the boundary ------------------------------------------------------------------------------------------------------------
+
+def test_header_declares_and_library_exports_the_level_set_entries(pdeip):
+    syms = declared_symbols()
+    lib = ctypes.CDLL(pdeip.capi.LIB_PATH)
+    for name in ENTRIES:
+        assert name in syms, name
+        assert hasattr(lib, name), name
+        assert name in pdeip.capi.SIGNATURES, name
+
+
+@pytest.mark.parametrize("name", LS_STUBS)
+def test_stub_compiles_and_checks_arity(pdeip, name):
+    lib = build_ls_stub(name, pdeip)
+    err, _ = call(lib, 1, [np.zeros((4, 4), np.float32)])
+    assert err is not None and "wrong number of input parameters" in err
+
+
+def test_ac_solver_stub_checks_types_and_outputs(pdeip):
+    lib = build_ls_stub("AC_solver_2d", pdeip)
+    z = np.zeros((5, 6), np.float32)
+    good = [z, z, z, z, np.float32(0.25), np.float32(1)]
+    bad = list(good)
+    bad[1] = z.astype(np.float64)
+    err, _ = call(lib, 1, bad)
+    assert err == "AC_solver_2D error: 'D_in' must be a noncomplex single-valued matrix."
+    bad = list(good)
+    bad[3] = z.astype(np.float64)
+    err, _ = call(lib, 1, bad)
+    assert err == "AC_solver_2D error: 'Diff_in' must be a noncomplex single-valued matrix."
+    bad = list(good)
+    bad[4] = np.float64(0.25)
+    err, _ = call(lib, 1, bad)
+    assert err == "AC_solver_2D error: 'tau' must be a noncomplex, single-type scalar"
+    err, _ = call(lib, 0, good)
+    assert "insufficient number of outputs" in err
+    err, _ = call(lib, 1, [np.zeros((1, 6), np.float32)] * 4 + good[4:])
+    assert "at least 2x2" in err  # refused by the library before any HIP call
+
+
+def test_reinit_stub_checks_types_and_outputs(pdeip):
+    lib = build_ls_stub("Reinit", pdeip)
+    z = np.zeros((5, 6), np.float32)
+    err, _ = call(lib, 1, [z.astype(np.float64), np.float32(1)])
+    assert err == "reInitC: 'PHI_in' must be a noncomplex single-valued matrix."
+    err, _ = call(lib, 1, [z, 1.0])
+    assert err == "reInitC error: 'T' must be a noncomplex, single-type scalar"
+    err, _ = call(lib, 0, [z, np.float32(1)])
+    assert "insufficient number of outputs" in err
+    err, _ = call(lib, 1, [np.zeros((6, 1), np.float32), np.float32(1)])
+    assert "at least 2x2" in err
+
+
+def test_reinit_without_steps_needs_no_gpu(pdeip):
+    """T <= 0 or NaN runs no step: the output is the input (and nothing reaches the device)."""
+    lib = build_ls_stub("Reinit", pdeip)
+    phi = np.asfortranarray(np.random.default_rng(1).standard_normal((7, 5, 2)).astype(np.float32))
+    for T in (0.0, -3.0, np.nan):
+        err, outs = call(lib, 1, [phi, np.float32(T)])
+        assert err is None and np.array_equal(outs[0], phi)
+        assert np.array_equal(pdeip.mex_api.Reinit(phi, np.float32(T)), phi)
+
+
+def test_mex_api_checks(pdeip):
+    api = pdeip.mex_api
+    z = np.zeros((5, 6), np.float32)
+    with pytest.raises(api.MexError, match="AC_solver_2D error: 'D_in' must be a noncomplex single-valued matrix"):
+        api.AC_solver_2d(z, z.astype(np.float64), z, z, np.float32(0.25), np.float32(1))
+    with pytest.raises(api.MexError, match="'nu' must be a noncomplex, single-type scalar"):
+        api.AC_solver_2d(z, z, z, z, np.float32(0.25), 1.0)
+    with pytest.raises(api.MexError, match="'D_in', 'GradNorm_in' and 'Diff_in' must have the size of 'PHI_in'"):
+        api.AC_solver_2d(z, z, np.zeros((5, 7), np.float32), z, np.float32(0.25), np.float32(1))
+    with pytest.raises(api.MexError, match="insufficient number of outputs"):
+        api.AC_solver_2d(z, z, z, z, np.float32(0.25), np.float32(1), nargout=0)
+    with pytest.raises(api.MexError, match="reInitC error: 'T' must be"):
+        api.Reinit(z, 10)
+
+
+@pytest.mark.parametrize("shape", [(1, 6), (6, 1), (1, 1)])
+def test_c_abi_refuses_lines_shorter_than_two(pdeip, shape):
+    capi = pdeip.capi
+    lib = capi.load()
+    z = np.zeros(shape, np.float32, order="F")
+    p = z.ctypes.data
+    rc = lib.pdeip_ac_solver(p, p, p, p, shape[0], shape[1], 1, 0.25, 1.0, p)
+    assert rc == capi.PDEIP_ERR_ARG and "at least 2x2" in capi.last_error()
+    rc = lib.pdeip_reinit(p, shape[0], shape[1], 1, 10.0, p)
+    assert rc == capi.PDEIP_ERR_ARG and "at least 2x2" in capi.last_error()
+    rc = lib.pdeip_ac_solver_dev(None, p, p, p, p, shape[0], shape[1], 1, 0.25, 1.0, p)
+    assert rc == capi.PDEIP_ERR_ARG
+    rc = lib.pdeip_reinit_dev(None, p, shape[0], shape[1], 1, 10.0, p)
+    assert rc == capi.PDEIP_ERR_ARG
+
+
+def test_c_abi_refuses_a_never_ending_reinit_loop(pdeip):
+    capi = pdeip.capi
+    lib = capi.load()
+    z = np.zeros((4, 4), np.float32, order="F")
+    p = z.ctypes.data
+    rc = lib.pdeip_reinit(p, 4, 4, 1, float(2 ** 25), p)
+    assert rc == capi.PDEIP_ERR_ARG and "never ends" in capi.last_error()
+
+
+def test_ac_solver_stub_checks_sizes(pdeip):
+    lib = build_ls_stub("AC_solver_2d", pdeip)
+    z = np.zeros((5, 6), np.float32)
+    err, _ = call(lib, 1, [z, z, np.zeros((5, 7), np.float32), z, np.float32(0.25), np.float32(1)])
+    assert err == "AC_solver_2D error: 'D_in', 'GradNorm_in' and 'Diff_in' must have the size of 'PHI_in'."
+
+
+@pytest.mark.parametrize("name,npar", [("GAC_v10a_gpu", 5), ("GAC_v10b_gpu", 4)])
+def test_gac_stubs_check_their_arguments(pdeip, name, npar):
+    lib = build_ls_stub(name, pdeip)
+    I = np.zeros((6, 7, 3), np.float32)
+    P = np.zeros((6, 7), np.float32)
+    prm = np.full(npar, np.nan)
+    err, _ = call(lib, 1, [I.astype(np.float64), P, prm])
+    assert err == "%s: 'Iin' must be a noncomplex single-valued matrix." % name
+    err, _ = call(lib, 1, [I, np.zeros((6, 8), np.float32), prm])
+    assert "'PHIin' must be a [rows x cols] matrix" in err
+    err, _ = call(lib, 1, [I, P, np.full(npar + 1, np.nan)])
+    assert err == "%s: 'params' must be a real double vector of %d elements" % (name, npar)
+    err, _ = call(lib, 0, [I, P, prm])
+    assert "insufficient number of outputs" in err
+    err, _ = call(lib, 1, [np.zeros((2, 7, 3), np.float32), np.zeros((2, 7), np.float32), prm])
+    assert "at least 3x3" in err  # refused by the library before any HIP call
+
+
+def test_gac_c_abi_refusals_need_no_gpu(pdeip):
+    capi = pdeip.capi
+    lib = capi.load()
+    z = np.zeros((8, 8), np.float32, order="F")
+    p = z.ctypes.data
+    assert lib.pdeip_gac(p, 8, 8, 1, p, 7, None, p) == capi.PDEIP_ERR_ARG and "model" in capi.last_error()
+    assert lib.pdeip_gac(p, 8, 8, 0, p, 0, None, p) == capi.PDEIP_ERR_ARG and "channels" in capi.last_error()
+    assert lib.pdeip_gac_dev(None, p, 2, 8, 1, p, 0, None, p) == capi.PDEIP_ERR_ARG
+
+
+def test_python_gac_drivers_reject_unknown_parameters(pdeip):
+    import importlib
+
+    drv = importlib.import_module("pde-based-image-processing_amd.drivers")
+    with pytest.raises(TypeError):
+        drv.GAC_v10b(np.zeros((8, 8), np.float32), np.zeros((8, 8), np.float32), c=0.1)
+    with pytest.raises(TypeError):
+        drv.GAC_v10a(np.zeros((8, 8), np.float32), np.zeros((8, 8), np.float32), alpha=1)
+
+
+def test_fixture_is_the_two_drivsco_images():
+    z = np.load(os.path.join(ROOT, "tests", "golden", "levelset", "drivsco.npz"))
+    assert z["I1"].shape == z["I2"].shape == (320, 400, 3) and z["I1"].dtype == np.uint8
+
+
+# ---- the restatement on its own ----------------------------------------------------------------------------------------------
+
+def _line_system(phi, d, g, diff, tau, nu):
+    """Tridiagonal system of one line in float64 (levelsetSolvers.c:700-742): sub a, diagonal b, super c, rhs."""
+    n = len(phi)
+    phi, d, g, diff = (np.asarray(x, np.float64) for x in (phi, d, g, diff))
+
+    def harm(k, q):
+        s = diff[k] + diff[q]
+        return 2 * tau * g[k] / s if s > 0 else 0.0
+
+    A = np.zeros((n, n))
+    for k in range(n):
+        dn = harm(k, k + 1) if k < n - 1 else 0.0
+        dp = harm(k, k - 1) if k > 0 else 0.0
+        A[k, k] = 2 + nu * (dn + dp)
+        if k > 0:
+            A[k, k - 1] = -nu * dp
+        if k < n - 1:
+            A[k, k + 1] = -nu * dn
+    return A, phi + tau * d
+
+
+def _problem(seed, nr, nc, nf=None):
+    rng = np.random.default_rng(seed)
+    shape = (nr, nc) if nf is None else (nr, nc, nf)
+    phi = rng.uniform(-3, 3, shape).astype(np.float32)
+    d = rng.uniform(-1, 1, shape).astype(np.float32)
+    g = rng.uniform(0.1, 1.5, shape).astype(np.float32)
+    diff = rng.uniform(0.2, 2.0, shape).astype(np.float32)
+    return [np.asfortranarray(x) for x in (phi, d, g, diff)]
+
+
+@pytest.mark.parametrize("shape", [(2, 2), (3, 5), (17, 11), (9, 23, 2)])
+def test_column_and_row_passes_solve_the_tridiagonal_systems(shape):
+    phi, d, g, diff = _problem(3, *shape)
+    tau, nu = 0.25, 1.7
+    col = ref.aos_column(phi, d, g, diff, tau, nu)
+    row = ref.aos_row(phi, d, g, diff, tau, nu, np.zeros_like(phi))
+    p3, d3, g3, f3 = (x if x.ndim == 3 else x[:, :, None] for x in (phi, d, g, diff))
+    c3 = col if col.ndim == 3 else col[:, :, None]
+    r3 = row if row.ndim == 3 else row[:, :, None]
+    for k in range(p3.shape[2]):
+        for j in range(p3.shape[1]):
+            A, rhs = _line_system(p3[:, j, k], d3[:, j, k], g3[:, j, k], f3[:, j, k], tau, nu)
+            np.testing.assert_allclose(c3[:, j, k], np.linalg.solve(A, rhs), rtol=1e-5, atol=1e-5)
+        for i in range(p3.shape[0]):
+            A, rhs = _line_system(p3[i, :, k], d3[i, :, k], g3[i, :, k], f3[i, :, k], tau, nu)
+            np.testing.assert_allclose(r3[i, :, k], np.linalg.solve(A, rhs), rtol=1e-5, atol=1e-5)
+
+
+def test_row_pass_adds_the_column_values():
+    phi, d, g, diff = _problem(4, 8, 9)
+    col = ref.aos_column(phi, d, g, diff, 0.25, 1.0)
+    alone = ref.aos_row(phi, d, g, diff, 0.25, 1.0, np.zeros_like(phi))
+    both = ref.aos_row(phi, d, g, diff, 0.25, 1.0, col)
+    assert np.array_equal(both, alone + col)
+
+
+def test_zero_diffusivity_rules():
+    """Column pass: a Diff == 0 pixel takes PHI_in.  Row pass: the pixel keeps its column value and the next pixel along the
+    row becomes PHI_in[next] + its column value; the last element of a line is never tested."""
+    phi, d, g, diff = _problem(5, 6, 7)
+    diff[2, 3] = 0
+    diff[5, 6] = 0  # last element of both its column and its row: never tested
+    col = ref.aos_column(phi, d, g, diff, 0.25, 1.0)
+    assert col[2, 3] == phi[2, 3]
+    row = ref.aos_row(phi, d, g, diff, 0.25, 1.0, col)
+    assert row[2, 4] == np.float32(phi[2, 4] + col[2, 4])
+    assert row[2, 3] == np.float32(col[2, 3] + 0)
+
+
+def test_reinit_reaches_a_signed_distance():
+    """A few hundred steps on a scaled, shifted cone bring |grad phi| to 1 away from the kink and the borders."""
+    n = 48
+    y, x = np.mgrid[0:n, 0:n].astype(np.float64)
+    r = np.hypot(x - 21.3, y - 25.7)
+    phi = np.asfortranarray((3.0 * (r - 12.0) + 0.4).astype(np.float32))
+    out = ref.Reinit(phi, np.float32(75))
+    assert ref.reinit_steps(75) == 300
+    gy, gx = np.gradient(out.astype(np.float64))
+    mag = np.hypot(gx, gy)
+    away = (r > 7) & (x > 3) & (x < n - 4) & (y > 3) & (y < n - 4)
+    err = np.abs(mag[away] - 1)
+    # the cone starts at |grad phi| = 3; the upwind scheme's own error is a few per cent at the front (central differences
+    # measure it here), so the bound is on 99 % of the pixels, with a looser one on all of them
+    assert np.percentile(err, 99) < 0.05 and err.max() < 0.1, (float(np.percentile(err, 99)), float(err.max()))
+    # the zero level set stays near r = 12
+    assert abs(float(np.mean(out[np.abs(r - 12) < 0.5]))) < 0.5
+
+
+def test_gac_lambda_is_matlabs_sorted_index():
+    x = np.arange(10, dtype=np.float32)[::-1].copy()
+    assert ref.gac_lambda(x) == 6  # round(0.7*10) = 7, 1-based -> the 7th smallest
+    y = np.array([np.nan, 3, 1, 2, 0], np.float32)
+    assert ref.gac_lambda(y) == 3  # sorted 0 1 2 3 NaN (NaN last); round(3.5) = 4 (half away from zero) -> 3
+    assert ref.gac_lambda(np.float32([5])) == 5
+
+
+def test_reinit_step_counts():
+    assert [ref.reinit_steps(T) for T in (0, 0.25, 10, 10.1, -1)] == [0, 1, 40, 41, 0]
+    assert ref.reinit_steps(np.nan) == 0
