@@ -564,6 +564,29 @@ int pdeip_reinit(const float *PHI, int nrows, int ncols, int nframes, float T, f
 int pdeip_ac_solver_dev(void *stream, const float *PHI, const float *D, const float *GradNorm, const float *Diff, int nrows,
                         int ncols, int nframes, float tau, float nu, float *PHI_out);
 int pdeip_reinit_dev(void *stream, const float *PHI, int nrows, int ncols, int nframes, float T, float *PHI_out);
+/* PHI_out = CV_solver_2d(PHI, D, DH, GradNorm, tau, nu) (mex/source/CV_solver_2d.c -> CV_AOSOMP_4_2d, levelsetSolvers.c:103,
+ * GRADNORM_ZERO_CHECK defined): one AOS step of the Chan-Vese model, bit-identical to the reference.  The gateway hands DH to
+ * the library's GradNorm_in slot and GradNorm to its Diff_in slot, so with g = GradNorm, delta = DH and q a line neighbour of p:
+ * w(p,q) = (g_p + g_q > 0) ? ((2*tau)*delta_p) / (g_p + g_q) : 0 (a NaN sum gives 0), right-hand side PHI + (tau*delta)*D, and
+ * a Thomas solve along every column (xc) and every row (xr), each chain running on its own solved x.  With i the row, j the
+ * column index and clamp(v) = "if (v > 5) v = 5; if (v < -5) v = -5;" (a NaN passes through):
+ *   col = (i >= 1 && g == 0) ? clamp(PHI) : clamp(0.0f + xc),   PHI_out = (j >= 1 && g == 0) ? clamp(PHI) : clamp(col + xr)
+ * (g == -0.0 counts as zero, a NaN g does not).  PHI_out must not alias an input. */
+int pdeip_cv_solver(const float *PHI, const float *D, const float *DH, const float *GradNorm, int nrows, int ncols, int nframes,
+                    float tau, float nu, float *PHI_out);
+/* The terms the segmentation drivers build for each CV_solver_2d call (DispSegmentation.m:380-387, DispSegmentationSparse.m:
+ * 388-396), this library's definition for single PHI (parity with MATLAB unpinned): DH = 1.0f / ((float)M_PI * (c0 + (PHI*PHI)
+ * / c1)), then if (DH < dh_floor) DH = dh_floor (a NaN dh_floor: no floor; a NaN DH stays NaN); GradNorm = sqrtf(dx*dx + dy*dy)
+ * with dx, dy = imfilter(PHI, [-1 0 1]*0.5, 'replicate') and its transpose, as the GAC drivers define them.  The drivers' forms:
+ * (c0, c1, dh_floor) = (1, 1, NaN) (generateSeeds), (1, 1, 0.06) (DispSegmentation), (2, 4, 0.04) (DispSegmentationSparse).
+ * nrows, ncols, nframes >= 1; the outputs must not alias PHI or each other. */
+int pdeip_cv_terms(const float *PHI, int nrows, int ncols, int nframes, float c0, float c1, float dh_floor, float *DH_out,
+                   float *GradNorm_out);
+/* Device-pointer forms, asynchronous on `stream`, workspace from the library's cache; no host read-back (graph-capturable). */
+int pdeip_cv_solver_dev(void *stream, const float *PHI, const float *D, const float *DH, const float *GradNorm, int nrows,
+                        int ncols, int nframes, float tau, float nu, float *PHI_out);
+int pdeip_cv_terms_dev(void *stream, const float *PHI, int nrows, int ncols, int nframes, float c0, float c1, float dh_floor,
+                       float *DH_out, float *GradNorm_out);
 /* PHIout = GAC_v10a(Iin, PHIin, param) / GAC_v10b(Iin, PHIin, param) (matlab/active_contour/GAC_v10a.m, GAC_v10b.m; runme.m:128-131):
  * the whole geodesic-active-contour driver in one call, resident on the device.  Iin: single [nrows x ncols x channels] (runme.m
  * divides by 255); PHIin: single [nrows x ncols]; PHIout: [nrows x ncols]; nrows, ncols >= 3.  model: PDEIP_GAC_A (balloon

@@ -28,7 +28,7 @@ UNITS = {
     "pdeip_host.hip": [],
     "pdeip_drivers.hip": [],
     "pdeip_multi.hip": [],
-    "pdeip_levelset.hip": ["pdeip_levelset.hpp"],
+    "pdeip_levelset.hip": ["pdeip_levelset.hpp", "pdeip_cv.hpp"],
 }
 # -ffp-contract=off is part of the parity contract (the reference is FMA-free C).
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]

@@ -125,6 +125,10 @@ SIGNATURES = {
     "pdeip_reinit_dev": [_P, _P, _I, _I, _I, _F, _P],
     "pdeip_gac": [_P, _I, _I, _I, _P, _I, _P, _P],
     "pdeip_gac_dev": [_P, _P, _I, _I, _I, _P, _I, _P, _P],
+    "pdeip_cv_solver": [_P, _P, _P, _P, _I, _I, _I, _F, _F, _P],
+    "pdeip_cv_terms": [_P, _I, _I, _I, _F, _F, _F, _P, _P],
+    "pdeip_cv_solver_dev": [_P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P],
+    "pdeip_cv_terms_dev": [_P, _P, _I, _I, _I, _F, _F, _F, _P, _P],
     # library state
     "pdeip_set_mode": [_I],
     "pdeip_get_mode": [],

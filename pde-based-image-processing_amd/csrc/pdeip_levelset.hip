@@ -2,13 +2,16 @@
 //
 //   PHI_out = AC_solver_2d(PHI, D, GradNorm, Diff, tau, nu)   mex/source/AC_solver_2d.c -> AC_AOS_4_2d   pdeip_ac_solver(_dev)
 //   PHI_out = Reinit(PHI, T)                                  mex/source/Reinit.c       -> reinit         pdeip_reinit(_dev)
+//   PHI_out = CV_solver_2d(PHI, D, DH, GradNorm, tau, nu)     mex/source/CV_solver_2d.c -> CV_AOSOMP_4_2d pdeip_cv_solver(_dev)
+//   [DH, gradPHI] of the segmentation drivers                                                            pdeip_cv_terms(_dev)
 //
-// Kernels: csrc/pdeip_levelset.hpp.  AOS has one order, so pdeip_set_mode does not apply.  Multi-frame inputs are planes
+// Kernels: csrc/pdeip_levelset.hpp, csrc/pdeip_cv.hpp.  AOS has one order, so pdeip_set_mode does not apply.  Multi-frame inputs are planes
 // solved independently, as in the reference.  Lines of any length are accepted (the reference stops at MAX_BUF_SIZE = 2048).
 //
 // Build (build.py): hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -c, one object per translation unit.
 #include "pdeip_ctx.hpp"
 #include "pdeip_levelset.hpp"
+#include "pdeip_cv.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -258,5 +261,91 @@ extern "C" int pdeip_gac(const float *Iin, int nrows, int ncols, int channels, c
     RC(upload(dP, PHIin, n));
     RC(pdeip_gac_dev(nullptr, dI, nrows, ncols, channels, dP, model, prm, dO));
     HIPCHK(hipMemcpy(PHIout, dO, n * sizeof(float), hipMemcpyDeviceToHost));
+    return PDEIP_OK;
+}
+
+// ---- PHI_out = CV_solver_2d(PHI, D, DH, GradNorm, tau, nu): the Chan-Vese AOS step (csrc/pdeip_cv.hpp) --------------------------
+extern "C" int pdeip_cv_solver_dev(void *stream, const float *PHI, const float *D, const float *DH, const float *GradNorm,
+                                   int nrows, int ncols, int nframes, float tau, float nu, float *PHI_out)
+{
+    const char *who = "pdeip_cv_solver_dev";
+    NONNULL(who, PHI); NONNULL(who, D); NONNULL(who, DH); NONNULL(who, GradNorm); NONNULL(who, PHI_out);
+    RC(check_ls_dims(who, nrows, ncols, nframes));
+    if (PHI_out == PHI || PHI_out == D || PHI_out == DH || PHI_out == GradNorm)
+        return set_err(PDEIP_ERR_ARG, "%s: PHI_out must not alias an input", who);
+    tls.last_launches = 0;
+    const size_t p = pad4((size_t)nrows * ncols * nframes);
+    float *ws = nullptr;
+    RC(ws_get(WS_LS, p * 6 * sizeof(float), &ws));
+    float *cpc = ws, *dpc = ws + p, *cpr = ws + 2 * p, *dpr = ws + 3 * p, *xc = ws + 4 * p, *xr = ws + 5 * p;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // column lanes and row lanes in one grid (their chains do not depend on each other), then the output rules
+    const int rb = (nrows + LS_BLOCK - 1) / LS_BLOCK, cb = (ncols + LS_BLOCK - 1) / LS_BLOCK;
+    hipLaunchKernelGGL(k_cv_lines, dim3((unsigned)(rb + cb), (unsigned)nframes), dim3(LS_BLOCK), 0, s, PHI, D, DH, GradNorm, xc, xr,
+                       cpc, dpc, cpr, dpr, nrows, ncols, rb, tau, nu);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_cv_combine, pixel_grid(nrows, ncols, nframes), dim3(256), 0, s, PHI, GradNorm, xc, xr, PHI_out, nrows, ncols);
+    HIPCHK(hipGetLastError());
+    tls.last_launches = 2;
+    return PDEIP_OK;
+}
+
+extern "C" int pdeip_cv_solver(const float *PHI, const float *D, const float *DH, const float *GradNorm, int nrows, int ncols,
+                               int nframes, float tau, float nu, float *PHI_out)
+{
+    const char *who = "cv_solver_2D";
+    NONNULL(who, PHI); NONNULL(who, D); NONNULL(who, DH); NONNULL(who, GradNorm); NONNULL(who, PHI_out);
+    RC(check_ls_dims(who, nrows, ncols, nframes));
+    RC(use_device());
+    const size_t nf = (size_t)nrows * ncols * nframes, p = pad4(nf);
+    float *ar = nullptr;
+    RC(ws_get(WS_ARENA, p * 5 * sizeof(float), &ar));
+    float *dP = ar, *dD = ar + p, *dH = ar + 2 * p, *dG = ar + 3 * p, *dO = ar + 4 * p;
+    RC(upload(dP, PHI, nf)); RC(upload(dD, D, nf)); RC(upload(dH, DH, nf)); RC(upload(dG, GradNorm, nf));
+    RC(pdeip_cv_solver_dev(nullptr, dP, dD, dH, dG, nrows, ncols, nframes, tau, nu, dO));
+    HIPCHK(hipMemcpy(PHI_out, dO, nf * sizeof(float), hipMemcpyDeviceToHost));
+    return PDEIP_OK;
+}
+
+namespace {
+int check_terms_args(const char *who, const float *PHI, int nrows, int ncols, int nframes, const float *DH_out, const float *G_out)
+{
+    if (nrows < 1 || ncols < 1 || nframes < 1)
+        return set_err(PDEIP_ERR_ARG, "%s: PHI must not be empty (got %dx%dx%d)", who, nrows, ncols, nframes);
+    if ((long long)nrows * ncols * nframes > 0x7fffffffLL) return set_err(PDEIP_ERR_ARG, "%s: more than 2^31-1 elements", who);
+    if (DH_out == PHI || G_out == PHI || DH_out == G_out)
+        return set_err(PDEIP_ERR_ARG, "%s: DH_out and GradNorm_out must not alias PHI or each other", who);
+    return PDEIP_OK;
+}
+} // namespace
+
+extern "C" int pdeip_cv_terms_dev(void *stream, const float *PHI, int nrows, int ncols, int nframes, float c0, float c1, float dh_floor,
+                                  float *DH_out, float *GradNorm_out)
+{
+    const char *who = "pdeip_cv_terms_dev";
+    NONNULL(who, PHI); NONNULL(who, DH_out); NONNULL(who, GradNorm_out);
+    RC(check_terms_args(who, PHI, nrows, ncols, nframes, DH_out, GradNorm_out));
+    hipLaunchKernelGGL(k_cv_terms, pixel_grid(nrows, ncols, nframes), dim3(256), 0, static_cast<hipStream_t>(stream), PHI, DH_out,
+                       GradNorm_out, nrows, ncols, c0, c1, dh_floor);
+    HIPCHK(hipGetLastError());
+    tls.last_launches = 1;
+    return PDEIP_OK;
+}
+
+extern "C" int pdeip_cv_terms(const float *PHI, int nrows, int ncols, int nframes, float c0, float c1, float dh_floor, float *DH_out,
+                              float *GradNorm_out)
+{
+    const char *who = "pdeip_cv_terms";
+    NONNULL(who, PHI); NONNULL(who, DH_out); NONNULL(who, GradNorm_out);
+    RC(check_terms_args(who, PHI, nrows, ncols, nframes, DH_out, GradNorm_out));
+    RC(use_device());
+    const size_t nf = (size_t)nrows * ncols * nframes, p = pad4(nf);
+    float *ar = nullptr;
+    RC(ws_get(WS_ARENA, p * 3 * sizeof(float), &ar));
+    float *dP = ar, *dH = ar + p, *dG = ar + 2 * p;
+    RC(upload(dP, PHI, nf));
+    RC(pdeip_cv_terms_dev(nullptr, dP, nrows, ncols, nframes, c0, c1, dh_floor, dH, dG));
+    HIPCHK(hipMemcpy(DH_out, dH, nf * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(GradNorm_out, dG, nf * sizeof(float), hipMemcpyDeviceToHost));
     return PDEIP_OK;
 }

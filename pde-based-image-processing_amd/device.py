@@ -206,6 +206,21 @@ def reinit(PHI, T, out):
     capi.call("pdeip_reinit_dev", _stream(), PHI.data_ptr(), nrows, ncols, F, float(T), out.data_ptr())
 
 
+def cv_solver(PHI, D, DH, GradNorm, tau, nu, out):
+    """out = one AOS step of the Chan-Vese model (CV_solver_2d); `out` must not alias an input."""
+    _chk(PHI, D, DH, GradNorm, out)
+    nrows, ncols, F = _dims(PHI)
+    capi.call("pdeip_cv_solver_dev", _stream(), *_p(PHI, D, DH, GradNorm), nrows, ncols, F, float(tau), float(nu), out.data_ptr())
+
+
+def cv_terms(PHI, c0, c1, dh_floor, DH_out, G_out):
+    """DH_out = 1/(pi*(c0 + PHI^2/c1)) floored at dh_floor (NaN: no floor), G_out = |grad PHI| (the segmentation drivers' terms)."""
+    _chk(PHI, DH_out, G_out)
+    nrows, ncols, F = _dims(PHI)
+    capi.call("pdeip_cv_terms_dev", _stream(), PHI.data_ptr(), nrows, ncols, F, float(c0), float(c1), float(dh_floor),
+              DH_out.data_ptr(), G_out.data_ptr())
+
+
 def fst_derivatives5(It0, It1, Idt, Idx, Idy):
     _chk(It0, It1, Idt, Idx, Idy)
     nrows, ncols, F = _dims(It0)

@@ -11,7 +11,7 @@ All arithmetic happens in libpdeip.so on the GPU; this file only checks, packs a
 
 Reference: Oflow_sor_elin4_2d.c, Oflow_sor_llin4_2d.c, Oflow_sor_llin8_2d.c, Oflow_lhs_elin4_2d.c,
 Oflow_lhs_llin4_2d.c, Disp_sor_llin4_2d.c, PDEsolver4.c, PDEsolver8.c, DdiffWeights.c,
-BilinInterp_2d.c, FstDerivatives5.c, SndDerivatives5.c, AC_solver_2d.c, Reinit.c (all under mex/source/).
+BilinInterp_2d.c, FstDerivatives5.c, SndDerivatives5.c, AC_solver_2d.c, Reinit.c, CV_solver_2d.c (all under mex/source/).
 """
 import numpy as np
 
@@ -272,6 +272,22 @@ def AC_solver_2d(PHI, D, GradNorm, Diff, tau, nu, nargout=1):
     out = _out_like(PHI)
     nrows, ncols = PHI.shape[:2]
     _run("pdeip_ac_solver", *[_ptr(a) for a in planes], nrows, ncols, _frames(PHI), tau, nu, _ptr(out))
+    return out
+
+
+def CV_solver_2d(PHI, D, DH, GradNorm, tau, nu, nargout=1):
+    """PHI_out = CV_solver_2d(PHI_in,D_in,DH_in,GradNorm_in,tau,nu)  -- mex/source/CV_solver_2d.c (-> CV_AOSOMP_4_2d)."""
+    who = "cv_solver_2D error"
+    planes = [_single(n, who, a) for n, a in (("PHI_in", PHI), ("D_in", D), ("DH_in", DH), ("GradNorm_in", GradNorm))]
+    tau, nu = _scalar("tau", who, tau), _scalar("nu", who, nu)
+    PHI = planes[0]
+    if any(a.size != PHI.size for a in planes[1:]):  # the rule and message of mex/levelset/CV_solver_2d.c
+        raise MexError(capi.PDEIP_ERR_ARG, "cv_solver_2D error: 'D_in', 'DH_in' and 'GradNorm_in' must have the size of 'PHI_in'.")
+    if nargout < 1:
+        raise MexError(capi.PDEIP_ERR_ARG, "cv_solver_2D error insufficient number of outputs. Outputs from this function is 'PHI_out'")
+    out = _out_like(PHI)
+    nrows, ncols = PHI.shape[:2]
+    _run("pdeip_cv_solver", *[_ptr(a) for a in planes], nrows, ncols, _frames(PHI), tau, nu, _ptr(out))
     return out
 
 
