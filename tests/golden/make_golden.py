@@ -1,10 +1,10 @@
 """Regenerates tests/golden/*.npz: inputs + expected outputs of every gateway on the hot path.
 
 PROVENANCE: the expected outputs are produced by this repository's CPU oracle (oracle/pdeip_oracle.c,
-a restatement of the reference's C library), NOT by the reference itself -- the reference cannot be
-built in this image (it needs MATLAB's mex.h/matrix.h) and ships no golden data.  The fixtures pin the
-oracle against accidental change and give the GPU tests committed vectors; they do not pin the oracle
-to the reference ("parity unpinned").
+a restatement of the reference's C library).  The fixtures pin the oracle against accidental change and
+give the GPU tests committed vectors; tests/test_ref_oracle.py replays every one of them through the
+reference's own gateways (oracle/_ref/, built by oracle/build_ref.py) and requires the same bits, so
+regenerated fixtures are checked against the reference too.
 
     python tests/golden/make_golden.py          # rewrites the fixtures
 """

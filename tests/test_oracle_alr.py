@@ -1,7 +1,7 @@
 """CPU: known-answer checks of the oracle's alternating line relaxation (solver = 2).
 
-Same idea as test_oracle_math.py: the reference cannot be built here, so what is pinned is the
-mathematics.  The line solvers treat EVERY pixel as an unknown and drop the neighbours that fall
+Same idea as test_oracle_math.py: besides the bit-for-bit pin to the reference's own gateways
+(test_ref_oracle.py), the mathematics is pinned.  The line solvers treat EVERY pixel as an unknown and drop the neighbours that fall
 outside the image (Neumann); their fixed point must be the float64 sparse direct solution of exactly
 that system, in the reference's line order and in the zebra order alike.
 """

@@ -1,7 +1,7 @@
 """CPU: known-answer checks of the oracle that do not come from the oracle itself.
 
-The reference ships no tests or golden data and cannot be built here, so the oracle's parity with it is
-unpinned; these tests pin the oracle's MATHEMATICS instead: the relaxation converges to the solution of
+The reference ships no tests or golden data; test_ref_oracle.py pins the oracle bit for bit to the reference's own
+gateways, and these tests pin the oracle's MATHEMATICS as well: the relaxation converges to the solution of
 the linear system the reference's formulas define (solved independently with a float64 sparse direct
 solver), both sweep orderings reach that solution within the north-star tolerance (1e-4 RMS), the
 residual/LHS operators agree with it, and the warp / weights match closed forms.
