@@ -129,6 +129,9 @@ SIGNATURES = {
     "pdeip_cv_terms": [_P, _I, _I, _I, _F, _F, _F, _P, _P],
     "pdeip_cv_solver_dev": [_P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P],
     "pdeip_cv_terms_dev": [_P, _P, _I, _I, _I, _F, _F, _F, _P, _P],
+    # nonlinear diffusion (csrc/pdeip_diffusion.hip)
+    "pdeip_diffusion4": [_P, _I, _I, _I, _P, _P],
+    "pdeip_diffusion4_dev": [_P, _P, _I, _I, _I, _P, _P],
     # library state
     "pdeip_set_mode": [_I],
     "pdeip_get_mode": [],

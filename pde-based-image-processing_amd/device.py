@@ -7,6 +7,8 @@ C-contiguous array [(F x) ncols x nrows].  Device planes are therefore torch flo
 shape [ncols, nrows] or [F, ncols, nrows]; `to_device` / `to_matlab` convert from/to the numpy
 arrays `mex_api` uses.  Kernels run on torch's current stream.
 """
+import ctypes
+
 import numpy as np
 import torch
 
@@ -219,6 +221,22 @@ def cv_terms(PHI, c0, c1, dh_floor, DH_out, G_out):
     nrows, ncols, F = _dims(PHI)
     capi.call("pdeip_cv_terms_dev", _stream(), PHI.data_ptr(), nrows, ncols, F, float(c0), float(c1), float(dh_floor),
               DH_out.data_ptr(), G_out.data_ptr())
+
+
+class Diffusion4Params(ctypes.Structure):
+    """pdeip_diffusion4_params: NaN keeps the driver's default (alpha 25, outer_iter 5)."""
+    _fields_ = [("alpha", ctypes.c_double), ("outer_iter", ctypes.c_double)]
+
+
+def diffusion4(I, alpha, outer_iter, out):
+    """out = Diffusion4_v10(I, 'alpha', alpha, 'outer_iter', outer_iter) before its uint8 cast (NaN: the driver's default);
+    `out` may be I itself (in place), otherwise I is not modified."""
+    _chk(I, out)
+    if out.shape != I.shape:
+        raise capi.PdeipError(capi.PDEIP_ERR_ARG, "diffusion4: out is %s but I is %s" % (tuple(out.shape), tuple(I.shape)))
+    nrows, ncols, C = _dims(I)
+    prm = Diffusion4Params(float(alpha), float(outer_iter))
+    capi.call("pdeip_diffusion4_dev", _stream(), I.data_ptr(), nrows, ncols, C, ctypes.addressof(prm), out.data_ptr())
 
 
 def fst_derivatives5(It0, It1, Idt, Idx, Idy):

@@ -13,6 +13,7 @@ capi.MODE_RED_BLACK the parallel one).
     DispEminND_llin_sym_2D      matlab/disparity/DispEminND_llin_sym_2D.m         symmetric stereo
     TVdenoise8 / TVdenoise4     matlab/denoising/TVdenoise{8,4}.m                 total-variation denoising
     GAC_v10a / GAC_v10b         matlab/active_contour/GAC_v10{a,b}.m              geodesic active contours (C++ only: pdeip_gac)
+    Diffusion4_v10              matlab/diffusion/Diffusion4_v10.m                 nonlinear diffusion (C++ only: pdeip_diffusion4)
 
 `Us=`, `Vs=` (param.Us / param.Vs: spatial a-priori fields, double, NaN = no constraint) and `scales=` (param.scales) are taken
 by the late-linearisation flow drivers and the disparity driver as the reference's drivers take them.
@@ -481,3 +482,30 @@ def GAC_v10b(Iin, PHIin, **param):
     """PHIout = GAC_v10b(Iin, PHIin, ...) (matlab/active_contour/GAC_v10b.m): geodesic active contour with the convection term
     grad(g) . grad(PHI); parameters as GAC_v10a without c."""
     return _gac(Iin, PHIin, 1, param)
+
+
+def uint8_matlab(x):
+    """MATLAB's uint8(x) of a float array: round half away from zero, saturate to 0..255, NaN -> 0.  (numpy's round is half
+    to even.)  In double, x + 0.5 is exact for every single x, so floor(x + 0.5) rounds the half away from zero once x >= 0."""
+    y = np.asarray(x, dtype=np.float64)
+    y = np.clip(np.where(np.isnan(y), 0.0, y), 0.0, 255.0)
+    return np.floor(y + 0.5).astype(np.uint8)
+
+
+def Diffusion4_v10(I_in, as_single=False, **param):
+    """Iout = Diffusion4_v10(I_in, ...) (matlab/diffusion/Diffusion4_v10.m): nonlinear (lagged-diffusivity) diffusion, the whole
+    run in one pdeip_diffusion4 call.  I_in [rows, cols(, C)] in any numeric type, taken as single(I_in); param: alpha (25),
+    outer_iter (5), as the driver names them.  Returns uint8(Iout) by MATLAB's rule, or the single Iout with as_single=True."""
+    import ctypes
+
+    for k in param:
+        if k not in ("alpha", "outer_iter"):
+            raise TypeError("Diffusion4_v10: unknown parameter %r" % k)
+    prm = dev.Diffusion4Params(float(param.get("alpha", math.nan)), float(param.get("outer_iter", math.nan)))
+    I = np.asfortranarray(np.asarray(I_in, dtype=np.float32))
+    if I.ndim not in (2, 3):
+        raise ValueError("Diffusion4_v10: I_in must be [rows, cols] or [rows, cols, C] (got %s)" % (I.shape,))
+    out = np.empty(I.shape, np.float32, order="F")
+    capi.call("pdeip_diffusion4", I.ctypes.data, I.shape[0], I.shape[1], I.shape[2] if I.ndim == 3 else 1, ctypes.addressof(prm),
+              out.ctypes.data)
+    return out if as_single else uint8_matlab(out)
