@@ -255,7 +255,7 @@ int run_sweeps(hipStream_t s, SweepPlanes<Mdl> P, int nrows, int ncols, int nfra
     vec = vec && aligned16(aux0) && aligned16(aux1);
     for (int f = 0; f < Mdl::NRO; f++) vec = vec && aligned16(P.ro[f]);
 
-    const int ntiles_r = (nrows + RB_OWN_ROWS - 1) / RB_OWN_ROWS;
+    const int ntiles_r = rb_row_tiles(nrows, RB_OWN_ROWS);
     const dim3 block(64 * RB_WAVES_PER_BLOCK);
     // Two sweeps per launch where the model allows it (pdeip_sor_rb.hpp, rb_march2): same results, about
     // two thirds of the traffic per sweep.  PDEIP_RB_FUSE=0 keeps one sweep per launch.

@@ -81,7 +81,7 @@ extern "C" int pdeip_pde_sor8_dev(void *stream, float *X, const float *TRACE, co
     static const bool fuse = env_int("PDEIP_RB_FUSE", 1) != 0; // two sweeps per launch (k_pde8_colour2), same results
     const int TJ1 = pick_rb_tj(nrows, ncols);
     int TJ2 = TJ1;
-    const int ntiles1 = (nrows + RB_OWN_ROWS - 1) / RB_OWN_ROWS, ntiles2 = (nrows + P8_OWN_ROWS2 - 1) / P8_OWN_ROWS2;
+    const int ntiles1 = rb_row_tiles(nrows, RB_OWN_ROWS), ntiles2 = rb_row_tiles(nrows, P8_OWN_ROWS2);
     if (fuse && iter >= 2) {
         // resident waves of the fused kernel (see pick_rb2_tj)
         const int slots = resident_waves(reinterpret_cast<const void *>(&k_pde8_colour2<true, false>), 64 * RB_WAVES_PER_BLOCK, RB_WAVES_PER_BLOCK);

@@ -109,7 +109,7 @@ k_pde8_colour(Pde8SweepPlanes P, float *dout0, float *dout1, int nrows, int ncol
     const int r = a * RB_OWN_ROWS - 4 + 4 * lane;
     const int j0 = b * TJ, j1 = (j0 + TJ < ncols) ? j0 + TJ : ncols;
     const float om1 = 1.0f - omega;
-    const bool store_lane = (lane >= 1) && (lane <= 62);
+    const bool store_lane = ((lane >= 1) && (lane <= 62)) || (lane == 63 && r == nrows - 1); // the bottom border row: see k_sor_rb
 
     float Om[4], Oc[4], Op[4];   // old X at columns c-1, c, c+1
     float Rmm[4], Rm[4];         // after stage 1, columns c-2, c-1
@@ -243,7 +243,7 @@ k_pde8_colour2(Pde8SweepPlanes P, float *dout0, float *dout1, int nrows, int nco
     const int r = a * P8_OWN_ROWS2 - 8 + 4 * lane;
     const int j0 = b * TJ, j1 = (j0 + TJ < ncols) ? j0 + TJ : ncols;
     const float om1 = 1.0f - omega;
-    const bool store_lane = (lane >= 2) && (lane <= 61);
+    const bool store_lane = ((lane >= 2) && (lane <= 61)) || (lane == 62 && r == nrows - 1); // the bottom border row: see k_sor_rb
 
     // windows relative to the column c of stage 1: O old at c-1,c,c+1; A after stage 1 at c-2,c-1; B after
     // sweep 1 at c-3,c-2; C after stage 3 at c-4,c-3; K coefficients at c..c-3

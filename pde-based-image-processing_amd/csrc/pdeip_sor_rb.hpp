@@ -28,6 +28,9 @@ namespace pdeip {
 
 constexpr int RB_OWN_ROWS = 248; // 62 storing lanes x 4 rows
 constexpr int RB_WAVES_PER_BLOCK = 4;
+// Row tiles of a frame for a kernel whose waves own `own` rows: the tiles cover rows 0 .. nrows-2, and the bottom border row goes
+// with the tile that owns row nrows-2, which it replicates (k_sor_rb, store_lane).
+constexpr int rb_row_tiles(int nrows, int own) { return (nrows - 1 + own - 1) / own; }
 #ifndef PDEIP_RB_NT
 #define PDEIP_RB_NT 0 /* measured at 4K: non-temporal coefficient loads are ~5 % slower than default-policy loads */
 #endif
@@ -579,7 +582,10 @@ k_sor_rb(SweepPlanes<Mdl> P, float *dout0, float *dout1, int nrows, int ncols, i
     gm.ncols = ncols;
     gm.col0 = col0;
     gm.omega = omega;
-    gm.store_lane = (lane >= 1) && (lane <= 62);
+    // The bottom border row is the replicate of row nrows-2.  Where it would be the FIRST row of a tile (nrows = 248 k + 1, never a
+    // vector frame), that tile's copy of row nrows-2 sits at the far end of its halo lane and is stale after the launch's
+    // half-sweeps; the launch logic makes no such tile (rb_row_tiles), and the tile above stores the row from its first halo lane.
+    gm.store_lane = ((lane >= 1) && (lane <= 62)) || (lane == 63 && gm.r == nrows - 1);
     // Alternate the marching direction from strip to strip: strips 2k and 2k+1 finish at their common
     // boundary together and strips 2k+1 and 2k+2 start at theirs together, so the halo columns both
     // sides need are touched at about the same time and the second toucher hits L1/L2 instead of HBM.

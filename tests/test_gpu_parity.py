@@ -248,10 +248,29 @@ def test_out_of_place_other_models(pdeip, oracle):
 def test_red_black_kernel_families_agree(pdeip, oracle, shape, small, pipe):
     """The three red-black kernel families -- one workgroup per small frame (k_sor_small), the four-sweep wave pipeline
     (k_sor_rbp) and the one/two-sweep marches (k_sor_rb) -- are selected by frame size; switched by hand they must all give
-    the oracle's colour-ordered result on the same frames, every 5-point model, iter 1..9, NaN-laced data."""
+    the oracle's colour-ordered result on the same frames, every 5-point model, iter 1..9, NaN-laced data.
+
+    The knobs only ALLOW a family: with the small path off and the pipeline on, a frame whose row count is not a multiple
+    of 4 -- (33,29), (17,30), (9,15), (135,240), (270,100) -- and every single-field model below 2^21 pixels still runs
+    k_sor_rb.  Which family a call ran is therefore asserted on its launch count, as the model of the launch logic in
+    seam_model.py predicts it (iter = 9: one launch of k_sor_small, three of a cut small frame or of the pipeline,
+    4 + 4 + 1, five of k_sor_rb)."""
     import os
 
+    import torch
+
+    import seam_model as sm
+
     api = pdeip.mex_api
+    lib = pdeip.capi.load()
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+
+    def ran(model, it, nframes=1):
+        family = sm.family_of(model, shape[0], shape[1], nframes, it, small=small == "1", pipe=pipe == "1", num_cus=cus)
+        want = sm.sweep_launches(family, model, shape[0], shape[1], nframes, it, cus)
+        got = lib.pdeip_last_launch_count()
+        assert got == want, "%s %s it=%d small=%s pipe=%s: %d launches, %s makes %d" % (model, shape, it, small, pipe, got, family, want)
+
     old = {k: os.environ.get(k) for k in ("PDEIP_RB_SMALL", "PDEIP_RB_PIPE")}
     os.environ["PDEIP_RB_SMALL"], os.environ["PDEIP_RB_PIPE"] = small, pipe
     api.set_mode(1)
@@ -261,16 +280,21 @@ def test_red_black_kernel_families_agree(pdeip, oracle, shape, small, pipe):
             p = pb.elin4(961, *shape, nan_frac=0.02)
             for g, w in zip(api.Oflow_sor_elin4_2d(*p.values(), f(it), f(1.9), f(1)), oracle.Oflow_sor_elin4_2d(*p.values(), it, 1.9, order=oracle.COLOUR)):
                 assert pb.bit_equal(g, w), "elin4 %s it=%d small=%s pipe=%s: %s" % (shape, it, small, pipe, pb.describe_mismatch(g, w))
+            ran("elin4", it)
             q = pb.llin4(962, *shape, nan_frac=0.02)
             for g, w in zip(api.Oflow_sor_llin4_2d(*q.values(), f(it), f(1.9), f(1)), oracle.Oflow_sor_llin4_2d(*q.values(), it, 1.9, order=oracle.COLOUR)):
                 assert pb.bit_equal(g, w), "llin4 %s it=%d" % (shape, it)
+            ran("llin4", it)
             d = pb.disp4(963, *shape, nan_frac=0.02)
             assert pb.bit_equal(api.Disp_sor_llin4_2d(*d.values(), f(it), f(1.9), f(1)), oracle.Disp_sor_llin4_2d(*d.values(), it, 1.9, order=oracle.COLOUR))
+            ran("disp4", it)
             e = pb.pde4(964, *shape, nframes=3, nan_frac=0.02)
             assert pb.bit_equal(api.PDEsolver4(*e.values(), f(it), f(1.75), f(1)), oracle.PDEsolver4(*e.values(), it, 1.75, order=oracle.COLOUR))
+            ran("pde4", it, 3)
             y = pb.dispsym4(965, *shape, nan_frac=0.02)
             for g, w in zip(api.Disp_sor_llin_sym4_2d(*y.values(), f(it), f(1.9), f(1)), oracle.Disp_sor_llin_sym4_2d(*y.values(), it, 1.9, order=oracle.COLOUR)):
                 assert pb.bit_equal(g, w)
+            ran("dispsym4", it)
     finally:
         api.set_mode(0)
         for k, v in old.items():

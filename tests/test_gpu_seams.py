@@ -1,0 +1,219 @@
+"""GPU: the fast orderings at FORCED strip widths, tile edges, plane alignments and kernel families, bit for bit against the
+oracle's colour (zebra) order.
+
+tests/seam_model.py states the cases and predicts each one's kernel family, the kernels its launch chain runs and its launch
+count from a model of the launch logic; tests/test_seam_matrix.py proves on the CPU that the lists reach every seam, counting a
+case only towards the kernels it really runs; this module runs the cases through the device entry points.  Where two families
+make different numbers of launches (four sweeps or more: the pipeline makes fewer than the marches, k_sor_small fewer still) a
+case that silently falls to another family fails on its launch count, whatever bits it produces; a call of fewer than four
+sweeps runs k_sor_rb whatever the knobs allow, and is labelled so.  The knobs are read by the library per call; every one is
+restored afterwards.
+"""
+import contextlib
+import functools
+import importlib
+import os
+
+import pytest
+
+import problems as pb
+import seam_model as sm
+
+pytestmark = pytest.mark.gpu
+
+KNOBS = ("PDEIP_RB_SMALL", "PDEIP_RB_PIPE", "PDEIP_RBP_TJ", "PDEIP_RB_TJ", "PDEIP_RBP_SERPENTINE", "PDEIP_ALR_SMALL", "PDEIP_ALR_PAIR")
+
+
+@contextlib.contextmanager
+def knobs(**kv):
+    """Set the given knobs (None: unset), clear the others, and put everything back."""
+    old = {k: os.environ.get(k) for k in KNOBS}
+    try:
+        for k in KNOBS:
+            v = kv.get(k)
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = str(v)
+        yield
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+# planes of each model in the order of its entry point: iterate fields, read-only fields, coefficient planes
+W4, W8 = ("wW", "wN", "wE", "wS"), ("wW", "wNW", "wN", "wNE", "wE", "wSE", "wS", "wSW")
+PLANES = {
+    "elin4": (("U", "V"), (), ("M", "Cu", "Cv", "Du", "Dv") + W4),
+    "llin4": (("dU", "dV"), ("U", "V"), ("M", "Cu", "Cv", "Du", "Dv") + W4),
+    "disp4": (("dU",), ("U",), ("Cu", "Du") + W4),
+    "pde4": (("X",), (), ("TRACE", "B") + W4),
+    "pde8": (("X",), (), ("TRACE", "B") + W8),
+}
+ENTRY = {"elin4": "pdeip_oflow_sor_elin4_dev", "llin4": "pdeip_oflow_sor_llin4_dev", "disp4": "pdeip_disp_sor_llin4_dev",
+         "pde4": "pdeip_pde_sor4_dev", "pde8": "pdeip_pde_sor8_dev"}
+OMEGA = {"elin4": 1.9, "llin4": 1.9, "disp4": 1.9, "dispsym4": 1.9, "pde4": 1.75, "pde8": 1.75}
+
+
+@functools.lru_cache(maxsize=2)
+def problem(model, nrows, ncols, nframes):
+    nan = 0.02 if nrows * ncols < sm.PIPE_MIN_PIXELS else 0.005
+    if model in ("pde4", "pde8"):
+        return getattr(pb, model)(4100, nrows, ncols, nframes=nframes, nan_frac=nan)
+    return getattr(pb, model)(4100, nrows, ncols, nan_frac=nan)
+
+
+def want_of(oracle, model, p, it, col0):
+    order = oracle.COLOUR | ((col0 & 1) << 1)
+    if model == "dispsym4":
+        return oracle.Disp_sor_llin_sym4_2d(*p.values(), it, OMEGA[model], solver=1, order=order)
+    fn = {"elin4": oracle.oflow_sor_elin4, "llin4": oracle.oflow_sor_llin4, "disp4": oracle.disp_sor_llin4, "pde4": oracle.pde_sor4,
+          "pde8": oracle.pde_sor8}[model]
+    out = fn(*p.values(), it, OMEGA[model], order)
+    return out if isinstance(out, tuple) else (out,)
+
+
+def offset_copy(t):
+    """The same plane at a 4-byte offset inside a larger device buffer: contiguous float32, not 16-byte aligned."""
+    import torch
+
+    flat = torch.empty(t.numel() + 8, dtype=torch.float32, device=t.device)
+    out = flat[1:1 + t.numel()].view(t.shape)
+    out.copy_(t)
+    assert out.data_ptr() % 16 == 4 and out.is_contiguous()
+    return out
+
+
+def run_point_case(pdeip, oracle, c):
+    import torch
+
+    dev, capi = importlib.import_module("pde-based-image-processing_amd.device"), pdeip.capi
+    lib = capi.load()
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    assert sm.expected_family(c, cus) == c.family, "the model sends this case to %s" % sm.expected_family(c, cus)
+    p = problem(c.model, c.nrows, c.ncols, c.nframes)
+    want = want_of(oracle, c.model, p, c.it, c.col0)
+    d = {k: dev.to_device(v) for k, v in p.items()}
+    env = dict(PDEIP_RB_SMALL=1 if c.small else 0, PDEIP_RB_PIPE=0 if c.group == "C" else 1, PDEIP_RBP_SERPENTINE=c.serp,
+               PDEIP_RBP_TJ=c.tj if c.family == "rbp" else None, PDEIP_RB_TJ=c.tj if c.group == "C" else None)
+    st = torch.cuda.current_stream().cuda_stream
+    tail = (c.nrows, c.ncols) + ((c.nframes,) if c.model in ("pde4", "pde8") else ()) + (c.it, OMEGA[c.model])
+    if c.model == "dispsym4":
+        assert c.inplace and c.role is None
+        with knobs(**env):
+            dev._chk(*d.values())
+            capi.call("pdeip_disp_sor_llin_sym4_dev", st, *[d[k].data_ptr() for k in p], *tail, 1, capi.MODE_RED_BLACK, c.col0)
+            launches = lib.pdeip_last_launch_count()
+        got = [d["dU0"], d["dU1"]]
+    else:
+        its, ros, cfs = PLANES[c.model]
+        if c.role == "iterate":
+            d[its[-1]] = offset_copy(d[its[-1]])
+        elif c.role == "readonly":
+            d[ros[0]] = offset_copy(d[ros[0]])
+        elif c.role == "coefficient":
+            d[cfs[-2]] = offset_copy(d[cfs[-2]])
+        outs = []
+        if not c.inplace:
+            outs = [torch.full_like(d[k], 7.0) for k in its]
+            if c.role == "destination":
+                outs[0] = offset_copy(outs[0])
+        dev._chk(*d.values(), *outs)
+        ptr = lambda names: [d[k].data_ptr() for k in names]
+        if c.model == "llin4":  # the read-only base flow comes first in its signature
+            args = ptr(ros) + ptr(its) + [o.data_ptr() for o in outs] + ptr(cfs)
+        elif c.model == "disp4":
+            args = ptr(ros) + ptr(its) + [o.data_ptr() for o in outs] + ptr(cfs)
+        else:
+            args = ptr(its) + [o.data_ptr() for o in outs] + ptr(cfs)
+        with knobs(**env):
+            capi.call(ENTRY[c.model] + ("" if c.inplace else "_to"), st, *args, *tail, capi.MODE_RED_BLACK, c.col0)
+            launches = lib.pdeip_last_launch_count()
+        got = [d[k] for k in its] if c.inplace else outs
+        if not c.inplace:
+            for k in its:
+                assert pb.bit_equal(dev.to_matlab(d[k]), p[k]), "%s: the input iterate %s was written" % (sm.case_id(c), k)
+    dev.sync_check()
+    geo = sm.case_geometry(c)
+    for k, (g, w) in enumerate(zip(got, want)):
+        g = dev.to_matlab(g)
+        assert pb.bit_equal(g, w), "%s field %d (%s): %s" % (sm.case_id(c), k, geo, pb.describe_mismatch(g, w))
+    assert launches == sm.expected_launches(c, cus), "%s: %d launches, %s predicts %d" % (sm.case_id(c), launches, c.family, sm.expected_launches(c, cus))
+
+
+@pytest.mark.parametrize("c", sm.CASES_A, ids=sm.case_id)
+def test_pipeline_at_forced_strip_widths(pdeip, oracle, c):
+    """k_sor_rbp, coupled models, PDEIP_RBP_TJ at the ends and the middle of the picker's range: ragged last strips of 1, 2 and
+    HALO -1/0/+1 columns, 1 / 2 / 3 / many strips, one lane to either side of every row-tile edge, forwards and mirrored; every
+    pipeline case runs four sweeps or more.  The three shorter calls run k_sor_rb with the pipeline allowed."""
+    run_point_case(pdeip, oracle, c)
+
+
+@pytest.mark.parametrize("c", sm.CASES_A_NARROW, ids=sm.case_id)
+def test_pipeline_at_widths_below_the_pickers_range(pdeip, oracle, c):
+    """PDEIP_RBP_TJ = 2, 3, 5: strips narrower than one halo, which the picker (8..1024) never chooses but the knob accepts."""
+    run_point_case(pdeip, oracle, c)
+
+
+@pytest.mark.parametrize("c", sm.CASES_B, ids=sm.case_id)
+def test_single_field_models_around_the_pipeline_switch(pdeip, oracle, c):
+    """disp4 / pde4 / dispsym4 enter k_sor_rbp from 2^21 pixels on: awkward frames above the switch at forced widths, three
+    frames of pde4, the frame one column below it, which must run k_sor_rb (twice the launches), and calls of one to three sweeps
+    above it, which are too short for the pipeline."""
+    run_point_case(pdeip, oracle, c)
+
+
+@pytest.mark.parametrize("c", sm.CASES_C, ids=sm.case_id)
+def test_marches_and_four_colour_kernels_at_forced_strip_widths(pdeip, oracle, c):
+    """k_sor_rb and k_pde8_colour / k_pde8_colour2 with PDEIP_RB_TJ in {2, 3, 12, 13, 64} (it sets the width of the one-sweep and
+    of the two-sweep kernel): vector and scalar forms, first and later launches of a call, tile edges at 248 and 240 rows."""
+    run_point_case(pdeip, oracle, c)
+
+
+@pytest.mark.parametrize("c", sm.CASES_D, ids=sm.case_id)
+def test_planes_at_a_four_byte_offset(pdeip, oracle, c):
+    """One plane of the call carved at a one-float offset out of a larger buffer, nrows a multiple of 4: the dispatch must leave the
+    16-byte kernels and give the oracle's bits.  That the dispatch NOTICED is shown by the launch count where the aligned twin of the
+    call would have run the pipeline: the elin4 and llin4 cases (coupled models enter it at any size) and disp4 at 1024x2048 make
+    the marches' count, not the pipeline's.  disp4 at 252x51 and pde8 run the same number of launches with vector or scalar accesses
+    (no frame separates the two for pde8: it has one chain), so those cases pin the bits of the scalar forms' callers only."""
+    run_point_case(pdeip, oracle, c)
+
+
+ALR_OMEGA = {"elin4": 1.5, "llin4": 1.4, "llin8": 1.4, "disp4": 1.4, "pde4": 1.3, "pde8": 1.3}
+ALR_ITERATE = {"elin4": ("U", "V"), "llin4": ("dU", "dV"), "llin8": ("dU", "dV"), "disp4": ("dU",), "pde4": ("X",), "pde8": ("X",)}
+
+
+@pytest.mark.parametrize("model", sm.ALR_MODELS)
+def test_zebra_kernels_on_small_and_degenerate_frames(pdeip, oracle, model):
+    """k_alr_zebra3 / k_alr_zebra3_pair (PDEIP_ALR_SMALL=0, coupled models also with PDEIP_ALR_PAIR=0) on the frames k_alr_small
+    otherwise takes -- 3x3, single tiles, lines of ALR_BLK -1/0/+1 elements -- and both sides of the 6144-pixel switch with
+    the knobs at their defaults; launch counts as pdeip_line.hip's run_alr makes them."""
+    dev, capi = importlib.import_module("pde-based-image-processing_amd.device"), pdeip.capi
+    lib = capi.load()
+    run = getattr(dev, {"elin4": "oflow_alr_elin4", "llin4": "oflow_alr_llin4", "llin8": "oflow_alr_llin8", "disp4": "disp_alr_llin4",
+                        "pde4": "pde_alr4", "pde8": "pde_alr8"}[model])
+    ref = getattr(oracle, run.__name__)
+    seen = set()
+    for c in [c for c in sm.alr_cases() if c.model == model]:
+        kw = dict(nan_frac=0.03)
+        if model in ("pde4", "pde8"):
+            kw["nframes"] = c.nframes
+        p = getattr(pb, model)(5200, c.nrows, c.ncols, **kw)
+        want = ref(*p.values(), c.it, ALR_OMEGA[model], oracle.COLOUR)
+        want = want if isinstance(want, tuple) else (want,)
+        d = {k: dev.to_device(v) for k, v in p.items()}
+        with knobs(PDEIP_ALR_SMALL=None if c.small else 0, PDEIP_ALR_PAIR=None if c.pair else 0):
+            run(*d.values(), c.it, ALR_OMEGA[model], capi.MODE_RED_BLACK)
+            launches = lib.pdeip_last_launch_count()
+        dev.sync_check()
+        for k, w in zip(ALR_ITERATE[model], want):
+            g = dev.to_matlab(d[k])
+            assert pb.bit_equal(g, w), "%s %s: %s" % (sm.case_id(c), k, pb.describe_mismatch(g, w))
+        expect = sm.alr_launches(model, c.nrows, c.ncols, c.it, small=c.small, pair=c.pair)
+        assert launches == expect, "%s: %d launches, run_alr makes %d" % (sm.case_id(c), launches, expect)
+        seen.add((c.small, launches == 1))
+    assert seen == {(False, False), (True, True), (True, False)}  # forced off; the small side of the switch; the other side
