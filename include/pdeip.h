@@ -85,7 +85,10 @@ int pdeip_release(void);
 int pdeip_last_launch_count(void);
 /* Changes whenever the library frees or regrows a cached workspace buffer (a larger frame, pdeip_release, pdeip_set_device).
  * A caller that captured *_dev calls into a HIP graph must re-capture when the value differs from the one at capture time:
- * the graph's kernel arguments point into those buffers. */
+ * the graph's kernel arguments point into those buffers.  Replaying a captured graph between eager calls is supported: nothing
+ * the library keeps on the host describes the content of a buffer that a replay rewrites (every exact-order call builds its own
+ * schedule table on its stream).  The *_dev calls share ONE set of scratch buffers per device: calls on different streams must
+ * be ordered by the caller. */
 int pdeip_workspace_generation(void);
 /* Waits for the device and reports PDEIP_ERR_DEVICE if a bounded dependency wait of the persistent
  * exact-order kernel (PDEIP_EXACT_PERSIST=1) timed out during the preceding calls. */

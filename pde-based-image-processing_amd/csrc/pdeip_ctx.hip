@@ -61,7 +61,6 @@ int ws_get(int slot, size_t bytes, float **out)
     if (d->ws_bytes[slot] < bytes) {
         HIPCHK(hipDeviceSynchronize());
         if (slot == WS_CTL) latch_abort(d);
-        if (slot == WS_ORDER) d->order_B = d->order_T = 0; // the cached schedule table goes with its buffer
         if (d->ws[slot]) {
             HIPCHK(hipFree(d->ws[slot]));
             g.ws_generation++;

@@ -478,14 +478,25 @@ struct PersistCtl {
     unsigned *ticket;    // [8] one per XCD list
     unsigned *abort_flag; // [1]
     unsigned *progress;  // [nframes][T][B] chunks completed and visible
-    const int *order;    // schedule table: [0..8] list offsets, [16..] items b | (t << 16) (pdeip_persist_host.hpp)
+    const int *order;    // schedule table: [0..8] list offsets, [9..10] stamp B, T, [16..] items b | (t << 16) (pdeip_persist_host.hpp)
     unsigned long long *mail; // [nframes][T][B][NIT][nrows] east-column results of a strip, {value, tag}: see "West edge" below
 };
 
+// Where the table's builder (k_persist_setup of every call; k_persist_order of the diagnostic entry point) stamps the shape of the
+// table it wrote: header ints 9 and 10 of ws[WS_ORDER].  The list kind is not stamped: a table of the right (B, T) is complete and
+// in dependency order with either kind, so a walker has nothing to refuse there.
+constexpr int PERSIST_STAMP_B = 9, PERSIST_STAMP_T = 10;
+
 // One item per workgroup (thread 0): the next one of the list of the XCD this workgroup runs on, or of the next list that still has
-// one (pdeip_persist_host.hpp).  Returns the item's index in the table and the frame, or false (cannot happen: one item per workgroup).
-__device__ __forceinline__ bool persist_take_item(const PersistCtl &ctl, int nframes, unsigned *item, unsigned *frame)
+// one (pdeip_persist_host.hpp).  Returns the item's index in the table and the frame, or false: the table in the buffer is not this
+// launch's (its stamp is not (B, T): the abort word is raised, nobody walks, pdeip_persist_error() reports PDEIP_ERR_DEVICE), or no
+// item is left (cannot happen: one item per workgroup).
+__device__ __forceinline__ bool persist_take_item(const PersistCtl &ctl, int nframes, int B, int T, unsigned *item, unsigned *frame)
 {
+    if (ctl.order[PERSIST_STAMP_B] != B || ctl.order[PERSIST_STAMP_T] != T) {
+        __hip_atomic_store(ctl.abort_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return false;
+    }
     const unsigned xcc = (unsigned)__builtin_amdgcn_s_getreg((3 << 11) | 20) & 7u; // HW_REG_XCC_ID, bits 3:0
     for (unsigned a = 0; a < 8; a++) {
         const unsigned x = (xcc + a) & 7u;
@@ -551,7 +562,7 @@ k_sor_exact_persist(SweepPlanes<Mdl> P, const float *pack, PersistCtl ctl, int n
     const bool mover = role == 1;
     if (threadIdx.x == 0) {
         unsigned item = 0, fr = 0;
-        s_ticket[2] = persist_take_item(ctl, nframes, &item, &fr) ? 1u : 0u;
+        s_ticket[2] = persist_take_item(ctl, nframes, B, T, &item, &fr) ? 1u : 0u;
         s_ticket[0] = item;
         s_ticket[1] = fr;
     }

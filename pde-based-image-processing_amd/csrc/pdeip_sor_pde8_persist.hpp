@@ -92,7 +92,7 @@ k_pde8_exact_persist(Pde8Planes P, const float *pack, float *side, PersistCtl ct
     const int role = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); // 0 compute, 1 loader, 2 storer, 3 west edge
     if (threadIdx.x == 0) {
         unsigned item = 0, fr = 0;
-        s_ticket[2] = persist_take_item(ctl, nframes, &item, &fr) ? 1u : 0u;
+        s_ticket[2] = persist_take_item(ctl, nframes, B, T, &item, &fr) ? 1u : 0u;
         s_ticket[0] = item;
         s_ticket[1] = fr;
     }

@@ -111,7 +111,7 @@ k_sor_walk(SweepPlanes<Mdl> P, const float *pack, PersistCtl ctl, int nrows, int
 
     if (threadIdx.x == 0) {
         unsigned item = 0, fr = 0;
-        s_ctl[2] = persist_take_item(ctl, nframes, &item, &fr) ? 1u : 0u;
+        s_ctl[2] = persist_take_item(ctl, nframes, B, T, &item, &fr) ? 1u : 0u;
         s_ctl[0] = item;
         s_ctl[1] = fr;
         s_ctl[4] = s_ctl[5] = 0u;

@@ -1,0 +1,557 @@
+"""GPU: what libpdeip.so and the Python layer carry from one call to the next -- the per-device workspace slots, the schedule
+table of the exact-order walkers, the sticky abort word, the cached HIP graphs -- pinned by SEQUENCES of calls, every result
+bit for bit against the oracle (liboracle.so) or the numpy statement of the operation (levelset_ref, cv_ref, diffusion_ref,
+oracle/matlab_side.py).
+
+1. a graph replayed between eager exact-order calls of another table shape (the sequences of tests/state_model.py; under the
+   parent's rules each of them walks a stale table: tests/test_state_model.py);
+2. a GraphedRun used again after the workspace was regrown or released;
+3. small, odd-shaped calls inside scratch slots that a large NaN-laced call of the same or of another family left dirty
+   (ws_get never shrinks a slot: a small call that reads scratch it did not write shows as NaN or as a bit difference);
+4. one fixed list of calls across all families in a shuffled order and in the reverse of it.
+"""
+import contextlib
+import importlib
+import os
+import random
+
+import numpy as np
+import pytest
+
+import cv_ref
+import diffusion_ref
+import levelset_ref as lr
+import problems as pb
+import state_model as sm
+from test_gpu_cv import _problem as cv_problem
+from test_gpu_diffusion import _image as diffusion_image
+from test_gpu_flow_level import frames as texture_frames, matlab_side
+from test_gpu_levelset import _drivsco, _problem as ls_problem
+
+pytestmark = pytest.mark.gpu
+F32 = np.float32
+
+
+def _sub(name):
+    return importlib.import_module("pde-based-image-processing_amd." + name)
+
+
+def _eq(got, want, what):
+    assert pb.bit_equal(got, want), "%s: %s" % (what, pb.describe_mismatch(got, want))
+
+
+def _ok(pdeip):
+    assert pdeip.capi.load().pdeip_persist_error() == 0, pdeip.capi.last_error()
+
+
+@contextlib.contextmanager
+def _env(values):
+    """Set environment knobs for the block and put back what was there (as test_gpu_persist.py does)."""
+    old = {k: os.environ.get(k) for k in values}
+    os.environ.update(values)
+    try:
+        yield
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+# model -> problem generator, device entry points (point SOR, line relaxation), the planes relaxed in place, host gateway
+MODELS = {
+    "elin4": dict(make=pb.elin4, sor="oflow_sor_elin4", alr="oflow_alr_elin4", out=("U", "V"), frames=False, gw="Oflow_sor_elin4_2d"),
+    "llin4": dict(make=pb.llin4, sor="oflow_sor_llin4", alr="oflow_alr_llin4", out=("dU", "dV"), frames=False, gw="Oflow_sor_llin4_2d"),
+    "llin8": dict(make=pb.llin8, sor=None, alr="oflow_alr_llin8", out=("dU", "dV"), frames=False, gw="Oflow_sor_llin8_2d"),
+    "disp4": dict(make=pb.disp4, sor="disp_sor_llin4", alr="disp_alr_llin4", out=("dU",), frames=None, gw="Disp_sor_llin4_2d"),
+    "pde4": dict(make=pb.pde4, sor="pde_sor4", alr="pde_alr4", out=("X",), frames=True, gw="PDEsolver4"),
+    "pde8": dict(make=pb.pde8, sor="pde_sor8", alr="pde_alr8", out=("X",), frames=True, gw="PDEsolver8"),
+}
+
+
+def _omega(model, solver):
+    return 1.4 if solver == 2 else (1.75 if model.startswith("pde") else 1.9)
+
+
+def _problem(model, seed, nrows, ncols, nframes=1, nan_frac=0.0):
+    m = MODELS[model]
+    if m["frames"] is None:
+        return m["make"](seed, nrows, ncols, nan_frac=nan_frac)
+    return m["make"](seed, nrows, ncols, nframes=nframes if m["frames"] else 1, nan_frac=nan_frac)
+
+
+def _tuple(x):
+    return tuple(x) if isinstance(x, (tuple, list)) else (x,)
+
+
+def _dev_run(model, d, it, mode, solver):
+    """The model's _dev entry point, in place on the iterate planes of d (a dict of device planes)."""
+    dev = _sub("device")
+    getattr(dev, MODELS[model]["sor" if solver == 1 else "alr"])(*d.values(), it, _omega(model, solver), mode)
+
+
+def _dev_want(oracle, model, p, it, mode, solver):
+    fn = getattr(oracle, MODELS[model]["sor" if solver == 1 else "alr"])
+    return _tuple(fn(*p.values(), it, _omega(model, solver), oracle.COLOUR if mode else oracle.LEX))
+
+
+def _dev_call(oracle, model, seed, nrows, ncols, nframes, it, mode, solver=1, nan_frac=0.0, compare=True, what=""):
+    """One device-pointer solver call on fresh planes; compared with the oracle unless it only serves to dirty the scratch."""
+    dev = _sub("device")
+    p = _problem(model, seed, nrows, ncols, nframes, nan_frac)
+    d = {k: dev.to_device(v) for k, v in p.items()}
+    _dev_run(model, d, it, mode, solver)
+    if not compare:
+        return
+    for k, w in zip(MODELS[model]["out"], _dev_want(oracle, model, p, it, mode, solver)):
+        _eq(dev.to_matlab(d[k]), w, "%s %s %dx%dx%d it=%d mode=%d solver=%d %s" % (what, model, nrows, ncols, nframes, it, mode, solver, k))
+
+
+def _host_call(pdeip, oracle, model, seed, nrows, ncols, nframes, it, mode, solver=1, nan_frac=0.0, compare=True, what=""):
+    """The host-pointer gateway of the model (it stages its planes through the library's scratch) in the ordering `mode`."""
+    api = pdeip.mex_api
+    api.set_mode(mode)
+    try:
+        p = _problem(model, seed, nrows, ncols, nframes, nan_frac)
+        gw, omega = MODELS[model]["gw"], _omega(model, solver)
+        got = _tuple(getattr(api, gw)(*p.values(), F32(it), F32(omega), F32(solver)))
+        if compare:
+            want = _tuple(getattr(oracle, gw)(*p.values(), it, omega, solver=solver, order=oracle.COLOUR if mode else oracle.LEX))
+            for k, (g, w) in enumerate(zip(got, want)):
+                _eq(g, w, "%s host %s %dx%dx%d it=%d mode=%d solver=%d out %d" % (what, model, nrows, ncols, nframes, it, mode, solver, k))
+    finally:
+        api.set_mode(0)
+
+
+# ---- 1. replay between eager calls ---------------------------------------------------------------------------------------------
+
+class _Graphed:
+    """graphs.GraphedRun around the exact-order _dev calls of `calls` (state_model.Call), in place on the captured input planes."""
+
+    def __init__(self, oracle, calls, seed):
+        dev, graphs = _sub("device"), _sub("graphs")
+        self.calls = calls
+        self.problems = [_problem(c.model, seed + 10 * k, c.nrows, c.ncols, c.nframes, nan_frac=0.01) for k, c in enumerate(calls)]
+        self.planes = [{k: dev.to_device(v) for k, v in p.items()} for p in self.problems]   # pristine: the run relaxes its own copies
+        self.want = [_dev_want(oracle, c.model, p, c.it, 0, 1) for c, p in zip(calls, self.problems)]
+        self.run = graphs.GraphedRun(self._fn)
+
+    def _fn(self, *ts):
+        outs, at = [], 0
+        for c, pl in zip(self.calls, self.planes):
+            d = dict(zip(pl.keys(), ts[at:at + len(pl)]))
+            at += len(pl)
+            _dev_run(c.model, d, c.it, 0, 1)
+            outs += [d[k] for k in MODELS[c.model]["out"]]
+        return tuple(outs)
+
+    def warm_up(self):
+        import torch
+
+        self._fn(*[t.clone() for pl in self.planes for t in pl.values()])
+        torch.cuda.synchronize()
+
+    def check(self, what):
+        dev = _sub("device")
+        outs = list(self.run(*[t for pl in self.planes for t in pl.values()]))
+        assert not self.run.failed and self.run.graph is not None, what + ": the capture fell back to eager calls"
+        for c, want in zip(self.calls, self.want):
+            for k, w in zip(MODELS[c.model]["out"], want):
+                _eq(dev.to_matlab(outs.pop(0)), w, "%s: graph %s %dx%d it=%d %s" % (what, c.model, c.nrows, c.ncols, c.it, k))
+
+
+def _eager_x(oracle, X, what):
+    _dev_call(oracle, X.model, 4100, X.nrows, X.ncols, X.nframes, X.it, 0, 1, nan_frac=0.01, what=what)
+
+
+@pytest.mark.parametrize("seq", sm.REPLAY_SEQUENCES, ids=lambda s: s.name)
+def test_replay_between_eager_calls(pdeip, oracle, seq):
+    """eager(X), replay(Y), eager(X), replay(Y), eager(X): a replay rewrites the walkers' schedule table behind the host's back,
+    and the eager call after it must still walk its own.  Every shape is warmed up first, so no slot regrows and the graph is
+    captured once."""
+    lib = pdeip.capi.load()
+    with _env(seq.env):
+        _eager_x(oracle, seq.X, seq.name + " warm-up")
+        g = _Graphed(oracle, seq.Y, 4200)
+        g.warm_up()
+        gen = lib.pdeip_workspace_generation()
+        g.check(seq.name + " capture")
+        for k in range(sm.REPLAYS):
+            _eager_x(oracle, seq.X, "%s eager X before replay %d" % (seq.name, k))
+            g.check("%s replay %d" % (seq.name, k))
+        _eager_x(oracle, seq.X, seq.name + " eager X after the last replay")
+        assert lib.pdeip_workspace_generation() == gen and g.run.generation == gen, "a slot regrew mid-sequence"
+        _ok(pdeip)
+
+
+# ---- 2. replay after regrow and after release ------------------------------------------------------------------------------------
+
+def test_graph_is_captured_again_after_regrow_and_release(pdeip, oracle):
+    """A larger eager call, or pdeip_release(), between two uses of a GraphedRun changes pdeip_workspace_generation(): the next use
+    re-captures (run.generation moves, run.failed stays False) and gives the oracle's bits; so does the eager call around it."""
+    lib = pdeip.capi.load()
+    seq, big = sm.REGROW, sm.REGROW_BIG
+    assert lib.pdeip_release() == 0   # whatever ran before: the slots start empty, so the big call below does regrow them
+    _eager_x(oracle, seq.X, "regrow: eager X")
+    g = _Graphed(oracle, seq.Y, 4300)
+    g.check("regrow: capture")
+    g.check("regrow: replay")
+    gen1 = g.run.generation
+    assert gen1 == lib.pdeip_workspace_generation()
+    _dev_call(oracle, big.model, 4310, big.nrows, big.ncols, big.nframes, big.it, 0, 1, nan_frac=0.01, what="regrow: the larger call")
+    assert lib.pdeip_workspace_generation() != gen1
+    g.check("regrow: first use after the larger call")
+    gen2 = g.run.generation
+    assert gen2 != gen1 and gen2 == lib.pdeip_workspace_generation()
+    _eager_x(oracle, seq.X, "regrow: eager X after the re-capture")
+    g.check("regrow: replay of the new graph")
+    assert g.run.generation == gen2
+    assert lib.pdeip_release() == 0
+    assert lib.pdeip_workspace_generation() != gen2
+    _eager_x(oracle, seq.X, "release: eager X")   # before the capture: X's slots are allocated again, nothing regrows under the new graph
+    g.check("release: first use after pdeip_release")
+    gen3 = g.run.generation
+    assert gen3 != gen2 and gen3 == lib.pdeip_workspace_generation()
+    _eager_x(oracle, seq.X, "release: eager X after the re-capture")
+    g.check("release: replay")
+    _eager_x(oracle, seq.X, "release: eager X after the replay")
+    assert g.run.generation == gen3
+    _ok(pdeip)
+
+
+# ---- 3. small calls inside oversized, dirty scratch ------------------------------------------------------------------------------
+# The large call comes right after pdeip_release(): it sizes every slot its family uses and leaves its own leftovers there, NaN
+# nearly everywhere (nan_frac 0.97).  The selections (quantile of ad_weights, lambda of the GAC drivers) get large FINITE data
+# instead: on an all-NaN plane they select nothing, which is not what these tests are after; their leftovers then differ from a
+# small call's values in every bit.
+BIG = (520, 700)
+NAN = 0.97
+SMALL_SOR = [(3, 3), (5, 300), (260, 7), (37, 53), (24, 40), (135, 240), (45, 500)]   # (24, 40): LDS-resident; (135, 240), (45, 500): cut, gated stores
+SMALL_ALR = [(3, 3), (5, 300), (260, 7), (37, 53), (64, 97)]
+SMALL_LS = [(3, 5), (37, 53), (61, 97), (23, 17, 3), (3, 2500), (260, 7)]
+SMALL_DIFF = [(2, 7), (37, 5), (37, 53, 3), (5, 300)]
+
+
+def _release(pdeip):
+    assert pdeip.capi.load().pdeip_release() == 0
+
+
+def _small_sor(oracle, model, mode, what):
+    for shape in SMALL_SOR:
+        for it in (1, 4):
+            _dev_call(oracle, model, 4400 + it, shape[0], shape[1], 3 if MODELS[model]["frames"] else 1, it, mode, 1, nan_frac=0.0, what=what)
+
+
+def _small_alr(oracle, model, mode, what):
+    for shape in SMALL_ALR:
+        for it in (1, 3):
+            _dev_call(oracle, model, 4500 + it, shape[0], shape[1], 3 if model == "pde4" else 1, it, mode, 2, nan_frac=0.0, what=what)
+
+
+@pytest.mark.parametrize("mode", [0, 1], ids=["exact", "red_black"])
+@pytest.mark.parametrize("model", ["elin4", "llin4", "disp4", "pde4", "pde8"])
+def test_small_point_sor_calls_in_dirty_scratch(pdeip, oracle, model, mode):
+    _release(pdeip)
+    _dev_call(oracle, model, 4401, BIG[0], BIG[1], 2, 5, mode, 1, nan_frac=NAN, compare=False)
+    _small_sor(oracle, model, mode, "after a large NaN call")
+    _ok(pdeip)
+
+
+@pytest.mark.parametrize("mode", [0, 1], ids=["reference_order", "zebra"])
+@pytest.mark.parametrize("model", ["elin4", "llin4", "llin8", "disp4", "pde4", "pde8"])
+def test_small_line_relaxation_calls_in_dirty_scratch(pdeip, oracle, model, mode):
+    _release(pdeip)
+    _dev_call(oracle, model, 4501, BIG[0], BIG[1], 2, 2, mode, 2, nan_frac=NAN, compare=False)
+    _small_alr(oracle, model, mode, "after a large NaN call")
+    _ok(pdeip)
+
+
+def _nan_lace(seed, arrays, frac=NAN):
+    rng = np.random.default_rng(seed)
+    for a in arrays:
+        a[rng.random(a.shape) < frac] = np.nan
+    return arrays
+
+
+def _big_level_sets():
+    """AC_solver_2d, Reinit and CV_solver_2d on 700 x 2600 x 2 (lines above 2048 elements both ways would be 2600 only: the long
+    and the short line paths both run), NaN nearly everywhere."""
+    import torch
+
+    dev = _sub("device")
+    shape = (700, 2600, 2)
+    phi, d, g, diff = _nan_lace(1, ls_problem(31, shape, nan_d=False))
+    P, D, G, Df = (dev.to_device(x) for x in (phi, d, g, diff))
+    out = torch.empty_like(P)
+    dev.ac_solver(P, D, G, Df, 0.25, 1.3, out)
+    dev.reinit(P, 1.0, out)
+    phi, d, dh, g = _nan_lace(2, cv_problem(32, shape, nan=False))
+    P, D, H, G = (dev.to_device(x) for x in (phi, d, dh, g))
+    dev.cv_solver(P, D, H, G, 0.5, 0.3, out)
+    torch.cuda.synchronize()
+
+
+def _small_level_sets(what):
+    import torch
+
+    dev = _sub("device")
+    for shape in SMALL_LS:
+        phi, d, g, diff = ls_problem(33, shape)
+        P, D, G, Df = (dev.to_device(x) for x in (phi, d, g, diff))
+        out = torch.empty_like(P)
+        dev.ac_solver(P, D, G, Df, 0.25, 1.3, out)
+        _eq(dev.to_matlab(out), lr.AC_solver_2d(phi, d, g, diff, F32(0.25), F32(1.3)), "%s: AC_solver_2d %s" % (what, shape))
+        dev.reinit(P, 1.0, out)
+        _eq(dev.to_matlab(out), lr.Reinit(phi, F32(1)), "%s: Reinit %s" % (what, shape))
+        phi, d, dh, g = cv_problem(34, shape, nan=False)
+        P, D, H, G = (dev.to_device(x) for x in (phi, d, dh, g))
+        dev.cv_solver(P, D, H, G, F32(0.5), F32(0.3), out)
+        _eq(dev.to_matlab(out), cv_ref.CV_solver_2d(phi, d, dh, g, F32(0.5), F32(0.3)), "%s: CV_solver_2d %s" % (what, shape))
+
+
+def test_small_level_set_calls_in_dirty_scratch(pdeip):
+    _release(pdeip)
+    _big_level_sets()
+    _small_level_sets("after large NaN level-set calls")
+    _ok(pdeip)
+
+
+def _big_diffusion():
+    import torch
+
+    dev = _sub("device")
+    (I,) = _nan_lace(3, [diffusion_image(35, BIG + (3,))])
+    t = dev.to_device(I)
+    dev.diffusion4(t, 15, 2, torch.empty_like(t))
+    torch.cuda.synchronize()
+
+
+def _small_diffusion(what):
+    import torch
+
+    dev = _sub("device")
+    for shape in SMALL_DIFF:
+        I = diffusion_image(36, shape)
+        t = dev.to_device(I)
+        out = torch.empty_like(t)
+        dev.diffusion4(t, 15, 2, out)
+        _eq(dev.to_matlab(out), diffusion_ref.Diffusion4_v10(I, alpha=15, outer_iter=2), "%s: Diffusion4_v10 %s" % (what, shape))
+
+
+def test_small_diffusion_calls_in_dirty_scratch(pdeip):
+    _release(pdeip)
+    _big_diffusion()
+    _small_diffusion("after a large NaN diffusion call")
+    _ok(pdeip)
+
+
+def _gac_crops():
+    """Small and odd crops of the first drivsco image around its initial box, the box cropped with them."""
+    imgs, PHI = _drivsco()
+    return [(np.asfortranarray(imgs[0][r0:r0 + nr, c0:c0 + nc]), np.asfortranarray(PHI[r0:r0 + nr, c0:c0 + nc]))
+            for r0, c0, nr, nc in ((30, 100, 37, 53), (20, 90, 61, 97), (35, 105, 23, 131))]
+
+
+def _small_gac(what):
+    D = _sub("drivers")
+    for I, PHI in _gac_crops():
+        assert (PHI > 0).any() and (PHI < 0).any()
+        _eq(D.GAC_v10a(I, PHI, ITER=5), lr.GAC(I, PHI, "a", ITER=5), "%s: GAC_v10a %s" % (what, I.shape))
+        _eq(D.GAC_v10b(I, PHI, ITER=5), lr.GAC(I, PHI, "b", ITER=5), "%s: GAC_v10b %s" % (what, I.shape))
+
+
+def test_small_gac_calls_in_dirty_scratch(pdeip):
+    D = _sub("drivers")
+    imgs, PHI = _drivsco()
+    _release(pdeip)
+    big = np.asfortranarray(np.kron(imgs[1], np.ones((2, 3, 1), F32)) * F32(1e3))   # finite and far from any image's values
+    D.GAC_v10b(big, np.asfortranarray(np.kron(PHI, np.ones((2, 3), F32))), ITER=3)
+    _small_gac("after a large GAC call")
+    _ok(pdeip)
+
+
+def _small_host(pdeip, oracle, what):
+    for model, mode, solver, shape, it in (("elin4", 0, 1, (37, 53), 4), ("elin4", 1, 1, (5, 300), 4), ("llin4", 1, 1, (260, 7), 3), ("llin8", 0, 2, (37, 53), 2),
+                                           ("disp4", 0, 1, (3, 3), 2), ("pde4", 1, 2, (37, 53), 2), ("pde8", 0, 1, (5, 300), 3), ("pde8", 1, 1, (260, 7), 4)):
+        _host_call(pdeip, oracle, model, 4600, shape[0], shape[1], 3, it, mode, solver, what=what)
+    api = pdeip.mex_api
+    phi, d, g, diff = ls_problem(37, (37, 53))
+    _eq(api.AC_solver_2d(phi, d, g, diff, F32(0.25), F32(1.3)), lr.AC_solver_2d(phi, d, g, diff, F32(0.25), F32(1.3)), what + ": host AC_solver_2d")
+    _eq(api.Reinit(phi, F32(1)), lr.Reinit(phi, F32(1)), what + ": host Reinit")
+    w = pb.warp(38, 37, 53, nframes=3)
+    _eq(api.BilinInterp_2d(w["Iin"], w["X"], w["Y"]), oracle.BilinInterp_2d(w["Iin"], w["X"], w["Y"]), what + ": host BilinInterp_2d")
+
+
+def test_small_host_calls_in_dirty_scratch(pdeip, oracle):
+    """The host-pointer entry points stage their planes through the library's scratch: large NaN-laced calls first, both orderings
+    and both solvers, then small ones."""
+    _release(pdeip)
+    for model, mode, solver in (("llin4", 0, 1), ("llin4", 1, 1), ("pde8", 0, 1), ("pde4", 1, 2)):
+        _host_call(pdeip, oracle, model, 4601, BIG[0], BIG[1], 3, 3, mode, solver, nan_frac=NAN, compare=False)
+    assert pdeip.capi.load().pdeip_persist_error() == 0
+    _small_host(pdeip, oracle, "after large NaN host calls")
+    _ok(pdeip)
+
+
+AD_SHAPES = [((37, 53), 1, 0.9), ((6, 120), 2, 0.5), ((131, 5), 1, 0.25), ((3, 5), 1, 0.9), ((64, 80), 3, 0.9)]
+
+
+def _small_ad_weights(what):
+    import torch
+
+    ms, dev = matlab_side(), _sub("device")
+    for shape, C, quantile in AD_SHAPES:
+        I0, _ = texture_frames(51 + C, shape[0], shape[1], C)
+        if C == 1:
+            I0 = np.asfortranarray(I0[:, :, 0])
+        w8 = [torch.empty((shape[1], shape[0]), device="cuda") for _ in range(8)]
+        dev.ad_weights(dev.to_device(I0), quantile, w8)
+        for k, (g, w) in enumerate(zip(w8, ms.ad_diff_weights(I0, quantile)[0])):
+            _eq(dev.to_matlab(g), w.astype(F32), "%s: AD weight %d %s C=%d q=%g" % (what, k, shape, C, quantile))
+
+
+def test_small_quantile_selections_in_dirty_scratch(pdeip):
+    import torch
+
+    dev = _sub("device")
+    _release(pdeip)
+    I0, _ = texture_frames(52, BIG[0], BIG[1], 3)
+    w8 = [torch.empty((BIG[1], BIG[0]), device="cuda") for _ in range(8)]
+    dev.ad_weights(dev.to_device(np.asfortranarray(I0 * F32(1e3))), 0.9, w8)   # finite, gradients a thousand times a small call's
+    torch.cuda.synchronize()
+    _small_ad_weights("after a large selection")
+    _ok(pdeip)
+
+
+def test_small_calls_of_one_family_in_the_scratch_of_another(pdeip, oracle):
+    """The large call of one family, then the small calls of another that shares a slot with it: the arena of the level sets, of
+    diffusion and of the host staging; the drivers' slot; the walkers' control block and the cut small frames' load counter."""
+    D = _sub("drivers")
+    # exact-order walkers of a coupled model, then the 9-point and a single-field walker and the red-black small path
+    _release(pdeip)
+    _dev_call(oracle, "elin4", 4701, BIG[0], BIG[1], 1, 5, 0, 1, nan_frac=NAN, compare=False)
+    _small_sor(oracle, "pde8", 0, "after a large exact-order elin4 call")
+    _small_sor(oracle, "disp4", 0, "after a large exact-order elin4 call")
+    _small_sor(oracle, "llin4", 1, "after a large exact-order elin4 call")
+    _ok(pdeip)
+    # level sets, then diffusion, the GAC drivers and line relaxation
+    _release(pdeip)
+    _big_level_sets()
+    _small_diffusion("after large NaN level-set calls")
+    _small_gac("after large NaN level-set calls")
+    _small_alr(oracle, "elin4", 1, "after large NaN level-set calls")
+    # diffusion, then the level sets and the selection
+    _release(pdeip)
+    _big_diffusion()
+    _small_level_sets("after a large NaN diffusion call")
+    _small_ad_weights("after a large NaN diffusion call")
+    # host staging, then device-pointer level sets, diffusion and line relaxation
+    _release(pdeip)
+    _host_call(pdeip, oracle, "llin4", 4702, BIG[0], BIG[1], 1, 3, 1, 1, nan_frac=NAN, compare=False)
+    _host_call(pdeip, oracle, "pde8", 4703, BIG[0], BIG[1], 3, 2, 0, 2, nan_frac=NAN, compare=False)
+    _small_level_sets("after large NaN host calls")
+    _small_diffusion("after large NaN host calls")
+    _small_alr(oracle, "pde8", 0, "after large NaN host calls")
+    # a resident driver, then small host calls, level sets and diffusion
+    _release(pdeip)
+    rng = np.random.default_rng(4704)
+    D.capi_TVdenoise8(np.asfortranarray(rng.random(BIG + (3,)).astype(F32) * F32(1e3)), outer_iter=2)
+    _small_host(pdeip, oracle, "after a large resident driver run")
+    _small_level_sets("after a large resident driver run")
+    _small_diffusion("after a large resident driver run")
+    _ok(pdeip)
+
+
+# ---- 4. order independence ---------------------------------------------------------------------------------------------------------
+# (kind, ...): "dev" / "host": model, nrows, ncols, nframes, it, mode, solver;  the rest: a shape (and a parameter)
+SEED = 20261017
+CALLS = [
+    ("dev", "elin4", 37, 53, 1, 4, 0, 1), ("dev", "elin4", 135, 240, 1, 4, 1, 1), ("dev", "elin4", 5, 300, 1, 9, 0, 1), ("dev", "elin4", 24, 40, 1, 9, 1, 1),
+    ("dev", "llin4", 260, 7, 1, 3, 0, 1), ("dev", "llin4", 68, 120, 1, 8, 1, 1), ("dev", "llin4", 97, 131, 1, 2, 0, 2), ("dev", "llin8", 64, 97, 1, 3, 1, 2),
+    ("dev", "disp4", 45, 330, 1, 3, 0, 1), ("dev", "disp4", 3, 3, 1, 1, 1, 1), ("dev", "disp4", 62, 63, 1, 3, 1, 2), ("dev", "pde4", 30, 60, 3, 2, 0, 1),
+    ("dev", "pde4", 45, 500, 2, 4, 1, 1), ("dev", "pde4", 37, 53, 3, 1, 0, 2), ("dev", "pde8", 50, 300, 2, 4, 0, 1), ("dev", "pde8", 244, 38, 1, 5, 1, 1),
+    ("dev", "pde8", 37, 53, 1, 1, 1, 2), ("dev", "elin4", 40, 150, 1, 4, 0, 1), ("dev", "elin4", 33, 230, 1, 3, 0, 1), ("dev", "elin4", 248, 37, 1, 5, 1, 1),
+    ("host", "elin4", 97, 131, 2, 4, 0, 1), ("host", "elin4", 64, 200, 1, 7, 1, 1), ("host", "llin4", 37, 53, 1, 5, 1, 1), ("host", "llin4", 131, 70, 1, 2, 0, 2),
+    ("host", "llin8", 32, 48, 1, 2, 1, 2), ("host", "disp4", 5, 300, 1, 6, 0, 1), ("host", "pde4", 260, 7, 2, 5, 1, 1), ("host", "pde8", 97, 131, 3, 3, 0, 1),
+    ("host", "pde8", 32, 48, 1, 4, 1, 1), ("host", "elin4", 388, 584, 1, 4, 0, 1),
+    ("ac", (61, 97)), ("ac", (23, 17, 3)), ("reinit", (37, 53)), ("reinit", (3, 2500)), ("cv", (61, 97, 2)), ("cv", (260, 7)),
+    ("diffusion", (37, 53, 3)), ("diffusion", (5, 300)), ("adw", (37, 53), 1, 0.9), ("adw", (6, 120), 2, 0.5),
+]
+
+
+def _run_listed(pdeip, oracle, k, call, cache):
+    """Run call k of CALLS and compare it with its reference (computed once per call and kept in `cache`)."""
+    import torch
+
+    dev, kind, what = _sub("device"), call[0], "call %d %s" % (k, call)
+    if kind in ("dev", "host"):
+        _, model, nrows, ncols, nframes, it, mode, solver = call
+        if kind == "host":
+            _host_call(pdeip, oracle, model, 4800 + k, nrows, ncols, nframes, it, mode, solver, nan_frac=0.01, what=what)
+            return
+        if k not in cache:
+            p = _problem(model, 4800 + k, nrows, ncols, nframes, 0.01)
+            cache[k] = (p, _dev_want(oracle, model, p, it, mode, solver))
+        p, want = cache[k]
+        d = {name: dev.to_device(v) for name, v in p.items()}
+        _dev_run(model, d, it, mode, solver)
+        for name, w in zip(MODELS[model]["out"], want):
+            _eq(dev.to_matlab(d[name]), w, what + " " + name)
+    elif kind in ("ac", "reinit"):
+        phi, d, g, diff = ls_problem(4800 + k, call[1])
+        P = dev.to_device(phi)
+        out = torch.empty_like(P)
+        if kind == "ac":
+            dev.ac_solver(P, dev.to_device(d), dev.to_device(g), dev.to_device(diff), 0.25, 1.3, out)
+            if k not in cache:
+                cache[k] = lr.AC_solver_2d(phi, d, g, diff, F32(0.25), F32(1.3))
+            want = cache[k]
+        else:
+            dev.reinit(P, 2.0, out)
+            if k not in cache:
+                cache[k] = lr.Reinit(phi, F32(2))
+            want = cache[k]
+        _eq(dev.to_matlab(out), want, what)
+    elif kind == "cv":
+        phi, d, dh, g = cv_problem(4800 + k, call[1])
+        P = dev.to_device(phi)
+        out = torch.empty_like(P)
+        dev.cv_solver(P, dev.to_device(d), dev.to_device(dh), dev.to_device(g), F32(0.5), F32(0.3), out)
+        if k not in cache:
+            cache[k] = cv_ref.CV_solver_2d(phi, d, dh, g, F32(0.5), F32(0.3))
+        _eq(dev.to_matlab(out), cache[k], what)
+    elif kind == "diffusion":
+        I = diffusion_image(4800 + k, call[1])
+        t = dev.to_device(I)
+        out = torch.empty_like(t)
+        dev.diffusion4(t, 20, 2, out)
+        if k not in cache:
+            cache[k] = diffusion_ref.Diffusion4_v10(I, alpha=20, outer_iter=2)
+        _eq(dev.to_matlab(out), cache[k], what)
+    elif kind == "adw":
+        _, shape, C, quantile = call
+        I0, _ = texture_frames(4800 + k, shape[0], shape[1], C)
+        if C == 1:
+            I0 = np.asfortranarray(I0[:, :, 0])
+        w8 = [torch.empty((shape[1], shape[0]), device="cuda") for _ in range(8)]
+        dev.ad_weights(dev.to_device(I0), quantile, w8)
+        if k not in cache:
+            cache[k] = [w.astype(F32) for w in matlab_side().ad_diff_weights(I0, quantile)[0]]
+        for j, (g, w) in enumerate(zip(w8, cache[k])):
+            _eq(dev.to_matlab(g), w, "%s weight %d" % (what, j))
+    else:
+        raise ValueError(call)
+
+
+def test_results_do_not_depend_on_the_order_of_calls(pdeip, oracle):
+    """The calls of CALLS -- every family, small / odd / mid-sized frames, both orderings (the host calls flip pdeip_set_mode), both
+    solvers, iteration counts 1..9 -- in a fixed shuffled order, then in the reverse of it: each result is the oracle's."""
+    assert len(CALLS) == 40
+    order = list(range(len(CALLS)))
+    random.Random(SEED).shuffle(order)
+    cache = {}
+    for k in order + order[::-1]:
+        _run_listed(pdeip, oracle, k, CALLS[k], cache)
+    assert pdeip.capi.get_mode() == 0
+    _ok(pdeip)

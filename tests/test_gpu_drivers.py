@@ -126,37 +126,81 @@ def test_disparity_driver_with_spatial_apriori(pdeip):
     assert -3.0 < m < -1.9 and abs(m + 2.0) < abs(float(np.median(base[10:-10, 20:-20])) + 2.0), m
 
 
+def _cached_runs(D):
+    """Every graphs.GraphedRun the drivers keep: drivers._GRAPHS[key], and for the FAS driver _GRAPHS[key]._graphs[...]."""
+    runs = []
+    for v in D._GRAPHS.values():
+        runs.extend(v._graphs.values() if hasattr(v, "_graphs") else [v])
+    return runs
+
+
+def _assert_captured(D, at_least):
+    """GraphedRun falls back to eager calls when a capture fails (failed = True): equal bits alone do not show that anything was
+    replayed.  Every cached run holds a captured graph and never fell back."""
+    runs = _cached_runs(D)
+    assert len(runs) >= at_least, (len(runs), at_least)
+    for r in runs:
+        assert r.failed is False and r.graph is not None, (r.failed, r.graph)
+    return len(runs)
+
+
 def test_graph_replay_gives_the_eager_bits(pdeip):
     """graph=True replays the run's launches from a captured HIP graph (graphs.py): the same bits as the eager run, on the
     first call (warm-up + capture + replay) and on later calls with new frames of the same size; row-major and column-major
-    numpy inputs take different upload paths (device.to_device) to the same device bytes."""
+    numpy inputs take different upload paths (device.to_device) to the same device bytes.  Every cached run really captured
+    (no eager fall-back), after its first call and after a replay."""
     I, _, _ = _yosemite255()
     D = drv()
+    lib = pdeip.capi.load()
+    n0 = len(_cached_runs(D))
     kw = dict(mode=pdeip.MODE_RED_BLACK, solver=1, omega=1.5)
     for frames in (I, np.asfortranarray(I[::-1].copy()), I[:, ::-1].copy()):
         want = D.FlowEminND_llin_2D_v10(frames, 1, "grad", "gradmag", **kw)
         got = D.FlowEminND_llin_2D_v10(frames, 1, "grad", "gradmag", graph=True, **kw)
         assert pb.bit_equal(got[0], want[0]) and pb.bit_equal(got[1], want[1]), pb.describe_mismatch(got[0], want[0])
+        _assert_captured(D, n0 + 1)
         want = D.FlowEminNDFASFMG_elin_2D_v10(frames, 1, solver=1, omega=1.0, **{"mode": pdeip.MODE_RED_BLACK})
         got = D.FlowEminNDFASFMG_elin_2D_v10(frames, 1, solver=1, omega=1.0, graph=True, **{"mode": pdeip.MODE_RED_BLACK})
         assert pb.bit_equal(got[0], want[0]) and pb.bit_equal(got[1], want[1])
+        _assert_captured(D, n0 + 2)
     # a larger frame regrows the library's scratch buffers (pdeip_workspace_generation changes): the cached graph is re-captured
     big = np.kron(I, np.ones((2, 2, 1), dtype=np.float32))
     D.FlowEminND_llin_2D_v10(big, 1, "grad", "gradmag", **kw)
     want = D.FlowEminND_llin_2D_v10(I, 1, "grad", "gradmag", **kw)
     got = D.FlowEminND_llin_2D_v10(I, 1, "grad", "gradmag", graph=True, **kw)
     assert pb.bit_equal(got[0], want[0]) and pb.bit_equal(got[1], want[1])
-    # exact order is captured too (round 3: the walkers' schedule table is built by a kernel on the call's stream, every scale its own
-    # shape, rebuilt by every call while capturing); twice: capture + replay, then a replay of the cached graph
+    _assert_captured(D, n0 + 2)
+    # exact order is captured too (the walkers' schedule table is built by a kernel on the call's stream, by every call, every scale
+    # its own shape); twice: capture + replay, then a replay of the cached graph.  Between the two an eager exact-order run of
+    # another frame size: a frame this narrow is one strip (B = 1) on every scale of its pyramid and every scale runs param.iter
+    # sweeps, so its first walker launch has the table shape of its last -- which is not what the replayed graph left in the schedule
+    # buffer (the full frame's finest scale is five strips).  tests/state_model.py (driver_events) models this sequence and
+    # tests/test_state_model.py shows it walks the stale table under the parent's rules.  The eager run gives its own bits before,
+    # between and after the replays.
+    import state_model as sm
+    assert I.shape[:2] == sm.DRIVER_FULL and D.ND_DEFAULTS["iter"] == sm.DRIVER_ITER
+    assert D.ND_DEFAULTS["firstLoop"] * D.ND_DEFAULTS["secondLoop"] == sm.DRIVER_LOOPS
+    small = np.ascontiguousarray(I[:sm.DRIVER_SMALL[0], :sm.DRIVER_SMALL[1]])
+    n1 = len(_cached_runs(D))
     b = D.FlowEminND_llin_2D_v10(I, 1, "rgb", "none", solver=1)
-    for _ in range(2):
+    bs = D.FlowEminND_llin_2D_v10(small, 1, "rgb", "none", solver=1)
+    for k in range(2):
         a = D.FlowEminND_llin_2D_v10(I, 1, "rgb", "none", solver=1, graph=True)
         assert pb.bit_equal(a[0], b[0]) and pb.bit_equal(a[1], b[1])
+        _assert_captured(D, n1 + 1)
+        s = D.FlowEminND_llin_2D_v10(small, 1, "rgb", "none", solver=1)
+        assert pb.bit_equal(s[0], bs[0]) and pb.bit_equal(s[1], bs[1]), "eager run after replay %d: %s" % (k, pb.describe_mismatch(s[0], bs[0]))
+        assert lib.pdeip_persist_error() == 0, pdeip.capi.last_error()
     b = D.FlowEminNDFASFMG_elin_2D_v10(I, 1, solver=1, omega=1.0)
-    for _ in range(2):
+    bs = D.FlowEminNDFASFMG_elin_2D_v10(small, 1, solver=1, omega=1.0)
+    for k in range(2):
         a = D.FlowEminNDFASFMG_elin_2D_v10(I, 1, solver=1, omega=1.0, graph=True)
         assert pb.bit_equal(a[0], b[0]) and pb.bit_equal(a[1], b[1])
-    assert pdeip.capi.load().pdeip_persist_error() == 0
+        _assert_captured(D, n1 + 2)
+        s = D.FlowEminNDFASFMG_elin_2D_v10(small, 1, solver=1, omega=1.0)
+        assert pb.bit_equal(s[0], bs[0]) and pb.bit_equal(s[1], bs[1]), "eager FAS run after replay %d: %s" % (k, pb.describe_mismatch(s[0], bs[0]))
+        assert lib.pdeip_persist_error() == 0, pdeip.capi.last_error()
+    assert lib.pdeip_persist_error() == 0
 
 
 def test_resident_cxx_drivers_equal_the_python_drivers(pdeip):
