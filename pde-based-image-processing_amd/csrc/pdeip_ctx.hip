@@ -16,22 +16,29 @@ int set_err(int code, const char *fmt, ...)
     return code;
 }
 
-SweepTimer::SweepTimer(hipStream_t stream) : s(stream)
+SweepTimer::SweepTimer(hipStream_t stream, int total_launches) : s(stream), total(total_launches)
 {
     if (!g.profile) return;
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone; // a captured launch is replayed, not run: nothing to time
+    if (hipStreamIsCapturing(s, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusNone) return;
     std::lock_guard<std::mutex> lock(g.ev_mutex);
     if (g.n_ev >= Context::MAX_EV) return;
     if (g.n_ev == g.n_ev_created) {
-        if (hipEventCreate(&g.ev[g.n_ev][0]) != hipSuccess || hipEventCreate(&g.ev[g.n_ev][1]) != hipSuccess) return;
+        // timing needs device-scope ordering only: no system-scope cache write-back and invalidate with the event
+        if (hipEventCreateWithFlags(&g.ev[g.n_ev][0], hipEventDisableSystemFence) != hipSuccess) return;
+        if (hipEventCreateWithFlags(&g.ev[g.n_ev][1], hipEventDisableSystemFence) != hipSuccess) {
+            (void)hipEventDestroy(g.ev[g.n_ev][0]);
+            return;
+        }
         g.n_ev_created++;
     }
     slot = g.n_ev++;
-    (void)hipEventRecord(g.ev[slot][0], s);
+    if (total == 0) (void)hipEventRecord(g.ev[slot][0], s);
 }
 void SweepTimer::stop(int launches)
 {
     if (slot < 0) return;
-    (void)hipEventRecord(g.ev[slot][1], s);
+    if (total == 0) (void)hipEventRecord(g.ev[slot][1], s);
     g.ev_launches[slot] = launches;
 }
 

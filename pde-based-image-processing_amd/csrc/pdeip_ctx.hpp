@@ -8,6 +8,7 @@
 #include "../../include/pdeip.h"
 
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 
 #include <atomic>
 #include <cstdarg>
@@ -91,13 +92,29 @@ int set_err(int code, const char *fmt, ...);
         if ((p) == nullptr) return ::pdeip::set_err(PDEIP_ERR_ARG, "%s: argument '%s' is NULL", who, #p); \
     } while (0)
 
-// Records an event pair around a run of sweep launches when profiling is on.
+// Times a run of sweep launches when profiling is on (pdeip_profile_*): from the first launch's begin to the last launch's end.
+// Two forms.  Where the number of launches is known before the first one (the red-black chain of run_sweeps) the two events are
+// handed to the launches themselves: launch_timed() binds start_for(i) / stop_for(i) -- null for all but the first and the last
+// launch -- to the kernel's own dispatch packet, so the timed stream carries the same packets as the untimed one.  Everywhere
+// else (exact order, k_sor_small, line relaxation, the persistent kernels) the constructor and stop() record the events as
+// markers around the launches.  No slot left (Context::MAX_EV), profiling off or a capturing stream: nothing is timed.
 struct SweepTimer {
     hipStream_t s;
     int slot = -1;
-    explicit SweepTimer(hipStream_t stream);
+    int total = 0; // launches of the call when the events ride on them; 0: recorded as markers
+    explicit SweepTimer(hipStream_t stream, int total_launches = 0);
+    hipEvent_t start_for(int launch) const { return (slot >= 0 && total > 0 && launch == 0) ? g.ev[slot][0] : nullptr; }
+    hipEvent_t stop_for(int launch) const { return (slot >= 0 && total > 0 && launch == total - 1) ? g.ev[slot][1] : nullptr; }
     void stop(int launches);
 };
+
+// A kernel launch that carries timing events on its own dispatch packet (hipExtLaunchKernelGGL); without events, the plain launch.
+template <class... KArgs, class... Args>
+inline void launch_timed(void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t lds, hipStream_t s, hipEvent_t start, hipEvent_t stop, Args... args)
+{
+    if (start == nullptr && stop == nullptr) hipLaunchKernelGGL(kernel, grid, block, lds, s, static_cast<KArgs>(args)...);
+    else hipExtLaunchKernelGGL(kernel, grid, block, (std::uint32_t)lds, s, start, stop, 0, static_cast<KArgs>(args)...);
+}
 
 // State of the device HIP is currently set to (the *_dev entry points work on whatever device the caller selected).
 DeviceState *cur_dev();

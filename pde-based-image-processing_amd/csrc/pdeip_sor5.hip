@@ -281,7 +281,10 @@ int run_sweeps(hipStream_t s, SweepPlanes<Mdl> P, int nrows, int ncols, int nfra
         return (launch & 1) ? bufA[f] : bufB[f];
     };
     auto buf_in = [&](int launch, int f) -> const float * { return launch == 0 ? bufA[f] : buf_out(launch - 1, f); };
-    SweepTimer timer(s);
+#ifndef PDEIP_TIMER_MARKERS
+#define PDEIP_TIMER_MARKERS 0 /* A/B aid: record the two events as markers around the chain, as every other path does */
+#endif
+    SweepTimer timer(s, PDEIP_TIMER_MARKERS ? 0 : total_launches); // the events ride on the first and the last launch: no packet of their own
     int nlaunch = 0, flips = 0; // flips: how many times the iterate changed buffers
     for (int it = 0; it < iter;) {
         if (pipe && it + PS <= iter) {
@@ -304,8 +307,9 @@ int run_sweeps(hipStream_t s, SweepPlanes<Mdl> P, int nrows, int ncols, int nfra
             // faster for it (97.7 vs 94.6 us, same run) -- the wave pipeline's step, not the memory system, sets its time.  Off.
             const int serp = env_int("PDEIP_RBP_SERPENTINE", 0);
             const int mirror_mode = serp < 0 || serp > 2 ? 0 : serp;
-            if (first) hipLaunchKernelGGL((k_sor_rbp<Mdl, PS, true>), pgrid, pblock, PL::LDS_BYTES, s, P, keep ? aux0 : nullptr, keep ? aux1 : nullptr, nrows, ncols, TJP, ntiles_p, nunits, omega, col0, n, mirror_mode);
-            else hipLaunchKernelGGL((k_sor_rbp<Mdl, PS, false>), pgrid, pblock, PL::LDS_BYTES, s, P, nullptr, nullptr, nrows, ncols, TJP, ntiles_p, nunits, omega, col0, n, mirror_mode);
+            hipEvent_t const e0 = timer.start_for(nlaunch), e1 = timer.stop_for(nlaunch);
+            if (first) launch_timed(&k_sor_rbp<Mdl, PS, true>, pgrid, pblock, PL::LDS_BYTES, s, e0, e1, P, keep ? aux0 : nullptr, keep ? aux1 : nullptr, nrows, ncols, TJP, ntiles_p, nunits, omega, col0, n, mirror_mode);
+            else launch_timed(&k_sor_rbp<Mdl, PS, false>, pgrid, pblock, PL::LDS_BYTES, s, e0, e1, P, nullptr, nullptr, nrows, ncols, TJP, ntiles_p, nunits, omega, col0, n, mirror_mode);
             if (first) {
                 P.cf[Mdl::D0] = aux0;
                 P.cf[Mdl::D1] = aux1;
@@ -326,7 +330,7 @@ int run_sweeps(hipStream_t s, SweepPlanes<Mdl> P, int nrows, int ncols, int nfra
         }
         const bool first = it == 0; // sweep 0 also builds the divisor planes
         float *d0 = first ? aux0 : nullptr, *d1 = first ? aux1 : nullptr;
-#define PDEIP_RB_LAUNCH(V, F, T) hipLaunchKernelGGL((k_sor_rb<Mdl, V, F, T>), grid, block, 0, s, P, d0, d1, nrows, ncols, TJ, ntiles_r, nunits, omega, col0, n)
+#define PDEIP_RB_LAUNCH(V, F, T) launch_timed(&k_sor_rb<Mdl, V, F, T>, grid, block, 0, s, timer.start_for(nlaunch), timer.stop_for(nlaunch), P, d0, d1, nrows, ncols, TJ, ntiles_r, nunits, omega, col0, n)
         if (two) {
             if (vec) { if (first) PDEIP_RB_LAUNCH(true, true, true); else PDEIP_RB_LAUNCH(true, false, true); }
             else     { if (first) PDEIP_RB_LAUNCH(false, true, true); else PDEIP_RB_LAUNCH(false, false, true); }
