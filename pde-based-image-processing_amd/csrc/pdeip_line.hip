@@ -192,6 +192,15 @@ struct AlrTwin {
     const float *orig[MAXP];
     float *twin[MAXP];
     int count = 0;
+    // twin[] is filled only after every plane is registered (alr_make_twins): membership is asked of orig[] alone -- asked through
+    // find(), an entry whose still unwritten twin happened to be null was registered twice, and a call of more than 16 planes
+    // then made a second transpose launch
+    bool has(const float *p) const
+    {
+        for (int k = 0; k < count; k++)
+            if (orig[k] == p) return true;
+        return false;
+    }
     float *find(const float *p) const
     {
         for (int k = 0; k < count; k++)
@@ -237,7 +246,7 @@ static int alr_make_twins(hipStream_t s, const Ctx *q, Ctx *qt, int nch, float *
     for (int c = 0; c < nch; c++) {
         memcpy(ptrs[c], &q[c], sizeof(Ctx));
         for (int k = 0; k < NP; k++)
-            if (ptrs[c][k] && !tw->find(ptrs[c][k])) {
+            if (ptrs[c][k] && !tw->has(ptrs[c][k])) {
                 if (tw->count == AlrTwin::MAXP) return set_err(PDEIP_ERR_ARG, "line relaxation: too many planes");
                 tw->orig[tw->count++] = ptrs[c][k];
             }

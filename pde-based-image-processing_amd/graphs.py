@@ -9,6 +9,8 @@ The library keeps scratch buffers whose addresses end up in the captured kernel 
 changes when one of them is freed or regrown, and the graph is captured again then.  The first call runs eagerly (it
 allocates those buffers and opts kernels into their LDS sizes, neither of which may happen during capture).
 """
+import gc
+
 import torch
 
 from . import capi
@@ -34,8 +36,18 @@ class GraphedRun:
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, stream=side):
-            out = self.fn(*self.static_in)
+        # No garbage collection inside the capture: a collector run that finds an unreachable graph or device tensor there (an
+        # earlier GraphedRun whose fn is a bound method of its owner is such a cycle) destroys it while the stream is capturing,
+        # and the runtime aborts the process.  Collect first, then keep the collector off until the capture has ended.
+        gc.collect()
+        gc_was_on = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.graph(g, stream=side):
+                out = self.fn(*self.static_in)
+        finally:
+            if gc_was_on:
+                gc.enable()
         torch.cuda.current_stream().wait_stream(side)
         self.graph, self.static_out = g, out
         self.generation = capi.load().pdeip_workspace_generation()

@@ -466,3 +466,160 @@ def coverage_gaps(cases=None, alr=None):
     return gaps
 
 
+# ---- the range-laced cases (tests/range_problems.py) --------------------------------------------------------------------------
+# The same families, forced by the same knobs, on problems whose divisors leave the range of ordinary numbers; run by
+# tests/test_gpu_range.py, and on the CPU (finite share, census, wave mix) by tests/test_range_problems.py.  A RangeCase wraps a
+# Case -- its group letter keeps its meaning for the knobs: A / B the pipeline, C the marches with PDEIP_RB_PIPE=0, D here the small
+# path with the knobs at their defaults -- and adds the relaxation factor and the lacing.  div_frac is the share of EACH of the three
+# out-of-range divisor classes: 0.002 leaves clean waves next to fallback waves in one launch of k_sor_rbp, 0 none that falls
+# back, 0.1 none that stays clean.
+RangeCase = namedtuple("RangeCase", "case omega frac div_frac corner")
+RANGE_SEED = 4200
+RANGE_OMEGA = {"elin4": 1.9, "llin4": 1.9, "llin8": 1.9, "disp4": 1.9, "dispsym4": 1.9, "pde4": 1.75, "pde8": 1.75}
+RANGE_MIXED, RANGE_CLEAN, RANGE_FALLBACK = 0.002, 0.0, 0.1
+# The cases that go through a gateway (exact order, line relaxation) compare the residual outputs too, and a residual is infinite
+# wherever the divisor data is: at the default share of 1 % per class the residual planes of the flow gateways are 98.99 % finite,
+# short of the 99 % every output plane of every case has to keep.  0.4 % per out-of-range divisor class leaves them above 99.5 %.
+RANGE_GATEWAY_DIV = 0.004
+from range_problems import CORNER_MIN_PIXELS  # class T: point SOR only, from this frame size on
+
+
+def corner_fits(model, nrows, ncols, it):
+    """Class T in colour order: a sweep is two half-sweeps (four quarter-sweeps of the 9-point model), and each carries a non-finite
+    value one pixel further, so after `it` sweeps the pixels within k it of the class's pixel can be non-finite, k = 2 (4) -- at most
+    (k it + 1)^2 of them inside the frame.  The case gets the class only where that is within the 1 % of a plane that may be
+    non-finite (and the frame has the 8192 pixels)."""
+    k = 4 if model == "pde8" else 2
+    return nrows * ncols >= max(CORNER_MIN_PIXELS, 100 * (k * it + 1) ** 2)
+
+
+def _r(case, omega, div_frac=None, frac=0.01):
+    # class T wherever the frame is large enough for it, but not where no wave is to fall back: its denominator is subnormal
+    return RangeCase(case, omega, frac, div_frac, corner_fits(case.model, case.nrows, case.ncols, case.it) and div_frac != RANGE_CLEAN)
+
+
+def _range_small():  # k_sor_small, knobs at their defaults: (37, 53) and (131, 70), iter 4 and 9
+    out = []
+    for mi, model in enumerate(("elin4", "llin4", "disp4", "dispsym4", "pde4")):
+        for si, (nrows, ncols) in enumerate(((37, 53), (131, 70))):
+            for ii, it in enumerate((4, 9)):
+                k = mi + si + ii
+                inplace = model == "dispsym4" or k % 2 == 0
+                out.append(_r(_c("D", "small", model, nrows, ncols, None, it, inplace=inplace, col0=(mi + ii) % 2, small=True),
+                              (1.0, RANGE_OMEGA[model])[(mi + si) % 2]))
+    return out
+
+
+def _range_rb():  # k_sor_rb and the four-colour kernels: PDEIP_RB_TJ in {3, 13}, iter 1, 2, 3 (one- and two-sweep kernels, first and later launches)
+    out = []
+    for mi, model in enumerate(("elin4", "llin4", "disp4", "dispsym4", "pde4", "pde8")):
+        for si, (nrows, ncols) in enumerate(((252, 51), (8, 139))):
+            for ii, it in enumerate((1, 2, 3)):
+                inplace = model in ("dispsym4", "pde8") or (mi + si) % 2 == 0
+                out.append(_r(_c("C", "pde8" if model == "pde8" else "rb", model, nrows, ncols, (3, 13)[(mi + si + ii) % 2], it, inplace=inplace,
+                                 col0=(si + ii) % 2), (1.0, RANGE_OMEGA[model])[(mi + ii) % 2]))
+    return out
+
+
+def _range_rbp():
+    out = []
+    # coupled models, clean waves beside fallback waves: TJ in {9, 33}, iter 4 and 9 (4 + 4 + 1), every serpentine mode, in place and _to, both col0
+    k = 0
+    for model in ("elin4", "llin4"):
+        for nrows, ncols in ((244, 300), (484, 57)):
+            for tj in (9, 33):
+                for it in (4, 9):
+                    out.append(_r(_c("A", "rbp", model, nrows, ncols, tj, it, inplace=(k // 3) % 2 == 0, col0=(k // 2) % 2, serp=k % 3),
+                                  (1.0, RANGE_OMEGA[model])[(k // 4 + k) % 2], RANGE_MIXED))
+                    k += 1
+    # single-field models at the 2^21 switch, one forced width each; disp4 also mirrored: its derive() is not symmetric in wW / wE
+    out += [_r(_c("B", "rbp", "disp4", 1024, 2048, 138, 4), 1.0, RANGE_MIXED),
+            _r(_c("B", "rbp", "disp4", 1024, 2048, 33, 9, inplace=False, col0=1, serp=1), 1.9, RANGE_MIXED),
+            _r(_c("B", "rbp", "disp4", 1024, 2048, 138, 4, serp=1), 1.0, RANGE_MIXED),
+            _r(_c("B", "rbp", "pde4", 1024, 2048, 138, 8, nframes=3, inplace=False, serp=2), 1.0, RANGE_MIXED),
+            _r(_c("B", "rbp", "dispsym4", 1024, 2048, 484, 4, col0=1), 1.0, RANGE_MIXED)]
+    # every wave clean, every wave falling back: with the mixed cases, the three outcomes of the ballot
+    for model in ("elin4", "llin4"):
+        out += [_r(_c("A", "rbp", model, 240, 67, 33, 4, col0=1, serp=2), 1.0, RANGE_CLEAN),
+                _r(_c("A", "rbp", model, 240, 67, 33, 5, inplace=False, serp=1), 1.0, RANGE_FALLBACK)]
+    for model in ("disp4", "pde4", "dispsym4"):
+        out += [_r(_c("B", "rbp", model, 1024, 2048, 138, 4), 1.0, RANGE_CLEAN),
+                _r(_c("B", "rbp", model, 1024, 2048, 138, 4, col0=1, serp=0 if model == "dispsym4" else 1), 1.0, RANGE_FALLBACK)]
+    return out
+
+
+RANGE_SMALL, RANGE_RB, RANGE_RBP = _range_small(), _range_rb(), _range_rbp()
+RANGE_CASES = RANGE_SMALL + RANGE_RB + RANGE_RBP
+
+
+def range_case_id(rc):
+    return "%s-w%g-d%s" % (case_id(rc.case), rc.omega, rc.div_frac)
+
+
+# Exact order, solver 1, through the gateways: every form of the wavefront kernels.  form -> the knobs that force it.
+EXACT_FORMS = {"persist": dict(PDEIP_EXACT_PERSIST=1, PDEIP_EXACT_WALK=0, PDEIP_PDE8_PERSIST=1), "front": dict(PDEIP_EXACT_PERSIST=0, PDEIP_PDE8_PERSIST=0),
+               "walk": dict(PDEIP_EXACT_PERSIST=1, PDEIP_EXACT_WALK=1)}
+RANGE_EXACT_MODELS = ("elin4", "llin4", "llin8", "disp4", "dispsym4", "pde4", "pde8")
+RANGE_EXACT_FRAMES = ((37, 53), (131, 70), (244, 300))
+RANGE_EXACT_OMEGAS, RANGE_EXACT_ITERS = (1.0, 1.9), (1, 4)
+ExactCase = namedtuple("ExactCase", "model nrows ncols nframes it omega corner")
+
+
+def exact_forms(model):
+    return ("persist", "front") if model == "pde8" else ("persist", "front", "walk")  # the 9-point walker has one persistent form
+
+
+def range_exact_cases(model):
+    return [ExactCase(model, r, c, 2 if model in ("pde4", "pde8") and (r, c) == (37, 53) else 1, it, om, r * c >= CORNER_MIN_PIXELS)
+            for r, c in RANGE_EXACT_FRAMES for om in RANGE_EXACT_OMEGAS for it in RANGE_EXACT_ITERS]
+
+
+def exact_launches(model, nrows, ncols, it, form):
+    """pdeip_last_launch_count() after an exact-order point-SOR call (run_sweeps, pdeip_pde_sor8_dev): the persistent forms make
+    three launches (pack the coefficients, walk, fill the borders); the launch-per-front form derives, then makes one launch per
+    front m = a + G b + H t of (row tiles of 64 steps) x (strips of 64 columns) x sweeps, then fills the borders."""
+    if it <= 0:
+        return 0
+    if form != "front":
+        n = 3
+    else:
+        skew, g, h = (2, 3, 4) if model == "pde8" else (1, 2, 3)
+        a, b = (nrows - 2 + skew * 63 + 63) // 64, (ncols - 2 + 63) // 64
+        n = 1 + ((a - 1) + g * (b - 1) + h * (it - 1) + 1) + 1
+    return 2 * n if model == "dispsym4" else n
+
+
+def alr_exact_launches(model, nrows, ncols, it):
+    """Exact order: launches of a line-relaxation call (run_alr, alr_lex_pass).  The coefficient planes transposed (one launch per
+    16), the factor planes of both directions (2), then per iteration a pass along the columns, the iterate transposed, a pass
+    along the rows, the iterate transposed back.  A pass of a coupled model walks both chains in one launch (k_alr_lex<2>) where two
+    lines of float4 fit the 160 KiB of LDS, and one chain per launch otherwise -- which is how a call shows the form it ran."""
+    nch, ntr, _ = ALR[model]
+    if model == "pde8":
+        it = 1
+    if it <= 0:
+        return 0
+    one_pass = lambda n: 1 if nch == 2 and 2 * 16 * n <= 160 * 1024 else nch
+    return _ceil(ntr, ALR_TB_MAX) + 2 + it * (one_pass(nrows) + 1 + one_pass(ncols) + 1)
+
+
+# Line relaxation, solver 2, no class T.  Exact order: pair and single chain (a line of 5200 elements holds one chain at a time).
+# Zebra: k_alr_small on (37, 53); k_alr_zebra3 / k_alr_zebra3_pair on (131, 70) and (226, 450) with PDEIP_ALR_SMALL=0, PDEIP_ALR_PAIR 0 / unset.
+RANGE_ALR_OMEGAS, RANGE_ALR_ITERS = (1.0, 1.4), (1, 3)
+RANGE_ALR_EXACT_FRAMES = ((37, 53), (131, 70), (7, 5200))
+RANGE_ALR_ZEBRA_FRAMES = ((37, 53, True), (131, 70, False), (226, 450, False))  # (nrows, ncols, k_alr_small allowed)
+AlrRangeCase = namedtuple("AlrRangeCase", "model nrows ncols nframes it omega zebra small pair")
+
+
+def range_alr_cases(model):
+    out = []
+    F = lambda r, c: 2 if model in ("pde4", "pde8") and (r, c) == (37, 53) else 1
+    for om in RANGE_ALR_OMEGAS:
+        for it in RANGE_ALR_ITERS:
+            for r, c in RANGE_ALR_EXACT_FRAMES:
+                out.append(AlrRangeCase(model, r, c, F(r, c), it, om, False, True, True))
+            for r, c, small in RANGE_ALR_ZEBRA_FRAMES:
+                out.append(AlrRangeCase(model, r, c, F(r, c), it, om, True, small, True))
+                if not small and ALR[model][0] == 2:
+                    out.append(AlrRangeCase(model, r, c, F(r, c), it, om, True, small, False))
+    return out

@@ -185,6 +185,32 @@ def test_replay_between_eager_calls(pdeip, oracle, seq):
         _ok(pdeip)
 
 
+def test_no_garbage_collection_inside_a_capture(pdeip):
+    """GraphedRun keeps Python's collector off while the stream is capturing and puts it back: a _Graphed above and its GraphedRun
+    refer to each other, so an earlier one is freed by the collector alone, and a collector run that starts inside a later capture
+    destroys that graph mid-capture -- the runtime aborts the process.  (torch.cuda.graph collects before a capture only where
+    torch.compiler.config.force_cudagraph_gc is set.)"""
+    import gc
+
+    import torch
+
+    seen = []
+
+    def fn(t):
+        seen.append(gc.isenabled())
+        return t + t
+
+    assert gc.isenabled()
+    run = _sub("graphs").GraphedRun(fn)
+    x = torch.arange(8, dtype=torch.float32, device="cuda")
+    out = run(x)
+    assert not run.failed and run.graph is not None
+    assert seen == [True, False] and gc.isenabled()  # the eager warm-up, then the capture
+    assert torch.equal(out, x + x)
+    out = run(x + 1)  # a replay runs no Python
+    assert seen == [True, False] and torch.equal(out, 2 * (x + 1))
+
+
 # ---- 2. replay after regrow and after release ------------------------------------------------------------------------------------
 
 def test_graph_is_captured_again_after_regrow_and_release(pdeip, oracle):
