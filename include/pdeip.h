@@ -33,6 +33,17 @@
  *   PDEIP_MODE_RED_BLACK    red-black (5-point) / four-colour (9-point) ordering with the
  *                           same per-pixel arithmetic: the throughput and multi-GPU mode.
  *                           Converges to the same fixed point; differs at finite `iter`.
+ *   PDEIP_MODE_LINE_SCAN    line relaxation (solver = 2) in the reference's line order and with
+ *                           its per-line coefficients, both Thomas recurrences of a line
+ *                           evaluated as a parallel scan over the workgroup.  Not bit-identical:
+ *                           within 1e-4 RMS per output plane of PDEIP_MODE_EXACT_ORDER from the
+ *                           first call on diagonally dominant lines, which is all the drivers
+ *                           produce (NaN in the coefficient planes Cu / TRACE is handled as in the
+ *                           other modes and is inside that contract).  A line that is not
+ *                           diagonally dominant, or that holds non-finite iterates, is outside
+ *                           it: the call returns and does not fault, its values are unspecified.
+ *                           Every entry point other than line relaxation behaves exactly as in
+ *                           PDEIP_MODE_EXACT_ORDER, bit for bit; no multi-GPU split.
  */
 #ifndef PDEIP_H
 #define PDEIP_H
@@ -50,11 +61,13 @@ extern "C" {
 
 #define PDEIP_MODE_EXACT_ORDER 0
 #define PDEIP_MODE_RED_BLACK 1
+#define PDEIP_MODE_LINE_SCAN 2
 
 /* `solver` argument of the solver gateways (e.g. Oflow_sor_elin4_2d.c:328-338).  Both are device paths:
  *   1 -> GS_SOR_*      point Gauss-Seidel SOR
  *   2 -> GS_ALR_SOR_*  alternating line relaxation (the MATLAB drivers' default); in PDEIP_MODE_EXACT_ORDER the
- *        reference's line order (bit-identical, serial by construction), in PDEIP_MODE_RED_BLACK zebra order. */
+ *        reference's line order (bit-identical, serial by construction), in PDEIP_MODE_RED_BLACK zebra order, in
+ *        PDEIP_MODE_LINE_SCAN the reference's line order with each line's recurrences as a parallel scan. */
 #define PDEIP_SOLVER_SOR 1
 #define PDEIP_SOLVER_ALR 2
 
@@ -280,6 +293,10 @@ int pdeip_pde_sor8_dev(void *stream, float *X, const float *TRACE, const float *
  *   mode PDEIP_MODE_EXACT_ORDER: the reference's line order, bit-identical, inherently serial (one
  *        workgroup per frame; a line of more than 10240 pixels is held in global memory instead of LDS: slow).
  *   mode PDEIP_MODE_RED_BLACK:   zebra order (even lines, then odd lines), lines solved concurrently.
+ *   mode PDEIP_MODE_LINE_SCAN:   the reference's line order; the two recurrences of a line are scans over one workgroup
+ *        (1e-4 RMS of EXACT_ORDER on diagonally dominant lines, values unspecified otherwise; see the top of this file).
+ *        Where the exact-order walker cannot hold its chains in LDS together (two coupled fields with lines of more than
+ *        5120 pixels, any line of more than 10240), and with PDEIP_ALR_SCAN=0, the call takes the EXACT_ORDER kernels.
  * pdeip_pde_alr8_dev runs ONE iteration whatever `iter` is, like the reference (pdeSolvers.c:362). */
 int pdeip_oflow_alr_elin4_dev(void *stream, float *U, float *V, const float *M, const float *Cu,
                               const float *Cv, const float *Du, const float *Dv, const float *wW,

@@ -13,6 +13,6 @@ or through the alias module `pdeip_amd` at the repository root.
 """
 from . import capi  # noqa: F401
 from . import mex_api  # noqa: F401
-from .capi import MODE_EXACT_ORDER, MODE_RED_BLACK, PdeipError  # noqa: F401
+from .capi import MODE_EXACT_ORDER, MODE_LINE_SCAN, MODE_RED_BLACK, PdeipError  # noqa: F401
 
-__all__ = ["capi", "mex_api", "MODE_EXACT_ORDER", "MODE_RED_BLACK", "PdeipError"]
+__all__ = ["capi", "mex_api", "MODE_EXACT_ORDER", "MODE_RED_BLACK", "MODE_LINE_SCAN", "PdeipError"]

@@ -17,6 +17,7 @@ PDEIP_ERR_DEVICE = 4
 PDEIP_ERR_NOMEM = 5
 MODE_EXACT_ORDER = 0
 MODE_RED_BLACK = 1
+MODE_LINE_SCAN = 2  # line relaxation in the reference's line order, a line's recurrences as parallel scans
 
 _P = ctypes.c_void_p  # float* (host or device), passed as an address
 _I = ctypes.c_int

@@ -1593,4 +1593,219 @@ __global__ void __launch_bounds__(ALR_LEX_THREADS) k_alr_lex(AlrChains<Mdl, NCH>
     if (sink == 1.2345e-30f) ch.c[0].x[0] = sink; // keeps the warm-up loads alive; never true in practice
 }
 
+// ------------------------------------------------------------------------------------------------
+// Reference line order, the recurrences of a line as scans (LINE_SCAN).
+//
+// Line order, factor planes and per-line coefficients are k_alr_lex's.  What differs is how the two recurrences of a line
+// are evaluated.  Both are first-order and LINEAR in the travelling value,
+//     dp[k] = (d[k] - dp[k-1] a[k]) div[k]  =  (-a[k] div[k]) dp[k-1] + d[k] div[k]          (a[0] = 0)
+//     x[k]  = dp[k] - cp[k] x[k+1]          =  (-cp[k])       x[k+1]  + dp[k]                (cp[n-1] = 0)
+// i.e. each element is an affine map y -> m y + t and a recurrence is the composition of its elements' maps, which is
+// associative:
+//   1. a lane holds 4 G consecutive elements (operands fetched 16 bytes at a time, Model::coef4) and composes them in order;
+//   2. one inclusive scan of the lanes' maps per wave: four DPP row shifts, then the three row totals by lane broadcast;
+//   3. the wave totals go through LDS; after a barrier every wave applies those before it, serially, to the entering 0;
+//      the two fields of a coupled solver are scanned side by side, each by its own half of the workgroup's waves (the second
+//      field one line behind the first, as in k_alr_lex), so a line step has the barriers and the memory latency of one line;
+//   4. the lane's entering value (its neighbour's inclusive map applied to the wave's entering value) runs through the
+//      lane's own elements.
+// The back-substitution is the same going down the line.  The first element (its divisor plane holds b), the last one (the
+// plain denominator) and the middle of a dividing south row (Mdl::SOUTH_TRUEDIV: the plain denominator too) multiply by a
+// reciprocal formed here.  Elements past the end of the line carry the identity map.  The SOR blend is applied in the
+// write-back.  Three barriers per line step; no line buffer: the elements stay in registers.  The shape of the tree depends
+// on the ALR_SCAN_* constants and G only.  (k_alr_lex's idle waves touch the next line's operands ahead of its build; here every
+// wave is busy, and the same loads issued between the barriers cost more than they saved: 11.8 against 9.5 us per 4K line step.)
+// ------------------------------------------------------------------------------------------------
+constexpr int ALR_SCAN_THREADS = ALR_LEX_THREADS;
+constexpr int ALR_SCAN_LANES = 64;
+constexpr int ALR_SCAN_WAVES = ALR_SCAN_THREADS / ALR_SCAN_LANES;
+constexpr int ALR_SCAN_VEC = 4;  // elements per group: one coef4
+constexpr int ALR_SCAN_MAXG = 3; // groups per lane at most: lines of up to 12 288 elements (6 144 for each of two coupled fields)
+
+struct AlrAff { // y -> m y + t
+    float m, t;
+};
+__device__ __forceinline__ AlrAff alr_then(const AlrAff &first, const AlrAff &second)
+{
+    return AlrAff{second.m * first.m, second.m * first.t + second.t};
+}
+// DPP move; a lane that has no source lane keeps `old`
+template <int CTRL> __device__ __forceinline__ float alr_dpp(float old, float v)
+{
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(v), CTRL, 0xf, 0xf, false));
+}
+template <int CTRL> __device__ __forceinline__ AlrAff alr_dpp_aff(const AlrAff &v)
+{ // the identity map where there is no source lane
+    return AlrAff{alr_dpp<CTRL>(1.0f, v.m), alr_dpp<CTRL>(0.0f, v.t)};
+}
+template <int LANE> __device__ __forceinline__ AlrAff alr_lane_aff(const AlrAff &v)
+{
+    return AlrAff{__int_as_float(__builtin_amdgcn_readlane(__float_as_int(v.m), LANE)),
+                  __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v.t), LANE))};
+}
+// Inclusive scan over the wave: lane u gets the composition of lanes 0..u (REV: of lanes 63 down to u, the higher lane first).
+template <bool REV> __device__ __forceinline__ AlrAff alr_scan_wave(AlrAff v, int lane)
+{
+    constexpr int SH = REV ? 0x100 : 0x110; // row_shl:n (lane u <- u + n) / row_shr:n (lane u <- u - n), within rows of 16 lanes
+    v = alr_then(alr_dpp_aff<SH + 1>(v), v);
+    v = alr_then(alr_dpp_aff<SH + 2>(v), v);
+    v = alr_then(alr_dpp_aff<SH + 4>(v), v);
+    v = alr_then(alr_dpp_aff<SH + 8>(v), v);
+    const int row = lane >> 4;
+    const AlrAff id{1.0f, 0.0f};
+    AlrAff acc = id;
+    if (REV) {
+        const AlrAff r3 = alr_lane_aff<48>(v), r2 = alr_lane_aff<32>(v), r1 = alr_lane_aff<16>(v);
+        acc = alr_then(acc, row < 3 ? r3 : id);
+        acc = alr_then(acc, row < 2 ? r2 : id);
+        acc = alr_then(acc, row < 1 ? r1 : id);
+    } else {
+        const AlrAff r0 = alr_lane_aff<15>(v), r1 = alr_lane_aff<31>(v), r2 = alr_lane_aff<47>(v);
+        acc = alr_then(acc, row > 0 ? r0 : id);
+        acc = alr_then(acc, row > 1 ? r1 : id);
+        acc = alr_then(acc, row > 2 ? r2 : id);
+    }
+    return alr_then(acc, v);
+}
+
+__device__ __forceinline__ void alr_st4(float *p, const float (&v)[4])
+{
+    alr_v4 t;
+    t.x = v[0]; t.y = v[1]; t.z = v[2]; t.w = v[3];
+    *reinterpret_cast<alr_v4 *>(p) = t;
+}
+
+template <class Mdl, int NCH, bool VERT, int G>
+__global__ void __launch_bounds__(ALR_SCAN_THREADS) k_alr_scan(AlrChains<Mdl, NCH> ch, int nrows, int ncols, size_t frame_stride, int lo, int hi,
+                                                               float omega)
+{
+    static_assert(G >= 1 && G <= ALR_SCAN_MAXG, "groups per lane");
+    static_assert(NCH == 1 || NCH == 2, "one field, or two coupled ones");
+    constexpr int E = ALR_SCAN_VEC * G;          // elements per lane
+    constexpr int TPC = ALR_SCAN_THREADS / NCH; // threads per chain: the chains of a coupled solver run side by side, each in its own waves
+    constexpr int WPC = ALR_SCAN_WAVES / NCH;
+    __shared__ float2 tot[2][NCH][WPC]; // wave totals: [forward / backward][chain][wave of the chain]
+    const int tid = threadIdx.x, lane = tid & (ALR_SCAN_LANES - 1);
+    const int c = NCH == 1 ? 0 : __builtin_amdgcn_readfirstlane(tid / TPC); // this wave's chain
+    const int wave = __builtin_amdgcn_readfirstlane((tid - c * TPC) / ALR_SCAN_LANES);
+    AlrChain<Mdl> me = ch.c[0];
+    if (NCH == 2 && c == 1) me = ch.c[NCH - 1];
+    const size_t fo = (size_t)blockIdx.x * frame_stride;
+    me.q.shift(fo);
+    me.x += fo;
+    me.cp += fo;
+    me.dv += fo;
+    const int n = VERT ? nrows : ncols, nlines = VERT ? ncols : nrows; // line l starts at l * n in either layout
+    const float om1 = 1.0f - omega;
+    const int k0 = (tid - c * TPC) * E; // this lane's first element
+
+    for (int s = lo; s <= hi + NCH - 1; ++s) {
+        const int l = s - c; // chain c trails chain 0 by c lines
+        const bool active = l >= lo && l <= hi; // wave-uniform
+        const size_t base = (size_t)(active ? l : lo) * n;
+        float m[E], t[E], cpk[E], xo[E];
+        AlrAff ex{1.0f, 0.0f}; // the map of the lanes before this one in its wave
+        // ---- the line's elements as affine maps; forward: the lane's composed, scanned over the wave ----
+        if (active) {
+            const bool tdiv = Mdl::SOUTH_TRUEDIV && !VERT && l == nrows - 1;
+            AlrAff sum{1.0f, 0.0f};
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                const int k = k0 + ALR_SCAN_VEC * g;
+                Tri r[ALR_SCAN_VEC];
+                float dv[ALR_SCAN_VEC], cp[ALR_SCAN_VEC], x[ALR_SCAN_VEC];
+                if (k + ALR_SCAN_VEC <= n) {
+                    Mdl::template coef4<VERT>(me.q, l, k, n, nlines, r);
+                    alr_ld4(me.dv + base + k, dv);
+                    alr_ld4(me.cp + base + k, cp);
+                    alr_ld4(me.x + base + k, x);
+                } else {
+#pragma unroll
+                    for (int e = 0; e < ALR_SCAN_VEC; ++e) {
+                        r[e] = Tri{0.0f, 1.0f, 0.0f, 0.0f};
+                        dv[e] = 1.0f;
+                        cp[e] = 0.0f;
+                        x[e] = 0.0f;
+                        if (k + e < n) {
+                            r[e] = line_coef<Mdl, VERT>(me.q, l, k + e, nrows, ncols);
+                            dv[e] = me.dv[base + k + e];
+                            cp[e] = me.cp[base + k + e];
+                            x[e] = me.x[base + k + e];
+                        }
+                    }
+                }
+#pragma unroll
+                for (int e = 0; e < ALR_SCAN_VEC; ++e) {
+                    const int kk = k + e, i = ALR_SCAN_VEC * g + e;
+                    const bool recip = kk == 0 || kk == n - 1 || tdiv;
+                    const float f = recip ? 1.0f / dv[e] : dv[e];
+                    m[i] = kk < n ? -(r[e].a * f) : 1.0f;
+                    t[i] = kk < n ? r[e].d * f : 0.0f;
+                    cpk[i] = kk < n - 1 ? cp[e] : 0.0f;
+                    xo[i] = x[e];
+                    sum = alr_then(sum, AlrAff{m[i], t[i]});
+                }
+            }
+            sum = alr_scan_wave<false>(sum, lane);
+            if (lane == ALR_SCAN_LANES - 1) tot[0][c][wave] = make_float2(sum.m, sum.t);
+            ex = alr_dpp_aff<0x138>(sum); // wave_shr:1: lane u <- u - 1, lane 0 the identity
+        }
+        __syncthreads();
+        // ---- forward fix-up: dp of every element; backward: the same with (-cp, dp), from the far end ----
+        if (active) {
+            float y = 0.0f; // the value entering this wave: the totals of the chain's waves before it, in order (all fetched at once)
+            float2 T[WPC];
+#pragma unroll
+            for (int w = 0; w < WPC; ++w) T[w] = tot[0][c][w];
+#pragma unroll
+            for (int w = 0; w < WPC - 1; ++w) y = (w < wave ? T[w].x : 1.0f) * y + (w < wave ? T[w].y : 0.0f);
+            y = ex.m * y + ex.t; // ... this lane
+            AlrAff sum{1.0f, 0.0f};
+#pragma unroll
+            for (int i = 0; i < E; ++i) {
+                y = m[i] * y + t[i]; // dp[k]
+                const bool in = k0 + i < n;
+                m[i] = in ? -cpk[i] : 1.0f;
+                t[i] = in ? y : 0.0f;
+            }
+#pragma unroll
+            for (int i = E - 1; i >= 0; --i) sum = alr_then(sum, AlrAff{m[i], t[i]});
+            sum = alr_scan_wave<true>(sum, lane);
+            if (lane == 0) tot[1][c][wave] = make_float2(sum.m, sum.t);
+            ex = alr_dpp_aff<0x130>(sum); // wave_shl:1: lane u <- u + 1, lane 63 the identity
+        }
+        __syncthreads();
+        // ---- backward fix-up, SOR blend, write-back ----
+        if (active) {
+            float y = 0.0f;
+            float2 T[WPC];
+#pragma unroll
+            for (int w = 0; w < WPC; ++w) T[w] = tot[1][c][w];
+#pragma unroll
+            for (int w = WPC - 1; w > 0; --w) y = (w > wave ? T[w].x : 1.0f) * y + (w > wave ? T[w].y : 0.0f);
+            y = ex.m * y + ex.t;
+            float out[E];
+#pragma unroll
+            for (int i = E - 1; i >= 0; --i) {
+                y = m[i] * y + t[i]; // x[k], unblended
+                out[i] = omega * y + om1 * xo[i];
+            }
+            float *x = me.x + base;
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                const int k = k0 + ALR_SCAN_VEC * g;
+                const float o4[ALR_SCAN_VEC] = {out[ALR_SCAN_VEC * g], out[ALR_SCAN_VEC * g + 1], out[ALR_SCAN_VEC * g + 2], out[ALR_SCAN_VEC * g + 3]};
+                if (k + ALR_SCAN_VEC <= n) {
+                    alr_st4(x + k, o4);
+                } else {
+#pragma unroll
+                    for (int e = 0; e < ALR_SCAN_VEC; ++e)
+                        if (k + e < n) x[k + e] = o4[e];
+                }
+            }
+        }
+        __syncthreads(); // the next lines' right-hand sides read these results
+    }
+}
+
 } // namespace pdeip

@@ -147,7 +147,7 @@ int check_dims(const char *who, int nrows, int ncols, int nframes)
 
 int check_mode(const char *who, int mode)
 {
-    if (mode != PDEIP_MODE_EXACT_ORDER && mode != PDEIP_MODE_RED_BLACK)
+    if (mode != PDEIP_MODE_EXACT_ORDER && mode != PDEIP_MODE_RED_BLACK && mode != PDEIP_MODE_LINE_SCAN)
         return set_err(PDEIP_ERR_ARG, "%s: unknown sweep ordering %d", who, mode);
     return PDEIP_OK;
 }
@@ -187,7 +187,7 @@ int pick_rb_tj(int nrows, int ncols)
 
 // Environment knobs of an unchanged MATLAB session: read once, before the first call
 // that needs them; explicit pdeip_set_mode / pdeip_set_device(s) calls made earlier win.
-//   PDEIP_MODE     exact | red_black (or 0 | 1)     sweep ordering of the host entry points
+//   PDEIP_MODE     exact | red_black | line_scan (or 0 | 1 | 2)   sweep ordering of the host entry points
 //   PDEIP_DEVICE   n                                HIP device of the host entry points
 //   PDEIP_DEVICES  a,b,c,...                        device group: red-black solver calls are split into column slabs
 static bool mode_set_explicitly = false, devices_set_explicitly = false;
@@ -200,7 +200,8 @@ void read_env_once()
     if (m && *m && !mode_set_explicitly) {
         if (!strcasecmp(m, "red_black") || !strcasecmp(m, "redblack") || !strcasecmp(m, "rb") || !strcmp(m, "1")) g.mode = PDEIP_MODE_RED_BLACK;
         else if (!strcasecmp(m, "exact") || !strcasecmp(m, "exact_order") || !strcmp(m, "0")) g.mode = PDEIP_MODE_EXACT_ORDER;
-        else fprintf(stderr, "libpdeip: PDEIP_MODE=%s not understood (exact | red_black); keeping exact order\n", m);
+        else if (!strcasecmp(m, "line_scan") || !strcasecmp(m, "linescan") || !strcmp(m, "2")) g.mode = PDEIP_MODE_LINE_SCAN;
+        else fprintf(stderr, "libpdeip: PDEIP_MODE=%s not understood (exact | red_black | line_scan); keeping exact order\n", m);
     }
     if (devices_set_explicitly) return;
     int ndev = 0;

@@ -73,10 +73,44 @@ static int alr_factor(hipStream_t s, const typename Mdl::Ctx *q, const typename 
     return PDEIP_OK;
 }
 
+// The fields a model's solver couples: the chains of one launch (elin4, llin4 and llin8 solve U and V together).
+template <class Mdl>
+constexpr int ALR_MODEL_CHAINS = (std::is_same<Mdl, AlrElin4>::value || std::is_same<Mdl, AlrLlin4>::value || std::is_same<Mdl, AlrLlin8>::value) ? 2 : 1;
+
+// LINE_SCAN: one launch of k_alr_scan per direction, all chains in it, G groups of four elements per lane.
+template <class Mdl, int NCH, bool VERT, int G>
+static int alr_scan_launch(hipStream_t s, const typename Mdl::Ctx *q, float *const *x, const AlrFactors &f, const int *order, int nrows, int ncols,
+                           int nframes, int lo, int hi, float omega)
+{
+    constexpr int d = VERT ? 0 : 1;
+    AlrChains<Mdl, NCH> ch;
+    for (int c = 0; c < NCH; c++) ch.c[c] = AlrChain<Mdl>{q[order[c]], x[order[c]], f.cp[order[c]][d], f.dv[order[c]][d]};
+    hipLaunchKernelGGL((k_alr_scan<Mdl, NCH, VERT, G>), dim3((unsigned)nframes), dim3(ALR_SCAN_THREADS), 0, s, ch, nrows, ncols, (size_t)nrows * ncols, lo,
+                       hi, omega);
+    tls.last_launches++;
+    HIPCHK(hipGetLastError());
+    return PDEIP_OK;
+}
+
+template <class Mdl, bool VERT>
+static int alr_scan_pass(hipStream_t s, const typename Mdl::Ctx *q, float *const *x, const AlrFactors &f, const int *order, int nrows, int ncols,
+                         int nframes, int lo, int hi, float omega)
+{
+    constexpr int NCH = ALR_MODEL_CHAINS<Mdl>;
+    const int n = VERT ? nrows : ncols;
+    const int per_group = ALR_SCAN_THREADS / NCH * ALR_SCAN_VEC; // elements one group per lane covers: the chains share the workgroup's threads
+    const int groups = (n + per_group - 1) / per_group;
+    if (groups <= 1) return alr_scan_launch<Mdl, NCH, VERT, 1>(s, q, x, f, order, nrows, ncols, nframes, lo, hi, omega);
+    if (groups == 2) return alr_scan_launch<Mdl, NCH, VERT, 2>(s, q, x, f, order, nrows, ncols, nframes, lo, hi, omega);
+    if (groups == 3) return alr_scan_launch<Mdl, NCH, VERT, 3>(s, q, x, f, order, nrows, ncols, nframes, lo, hi, omega);
+    return set_err(PDEIP_ERR_UNSUPPORTED, "line relaxation: no scan kernel for lines of %d elements", n);
+}
+
 // One direction, reference line order, for the `nch` fields in `order` (chain 1 trails chain 0 by a line).
+// scan: LINE_SCAN, k_alr_scan (run_alr decides per call).
 template <class Mdl>
 static int alr_lex_pass(hipStream_t s, const typename Mdl::Ctx *q, float *const *x, const AlrFactors &f, const int *order,
-                        int nch, int nrows, int ncols, int nframes, bool vertical, float omega)
+                        int nch, int nrows, int ncols, int nframes, bool vertical, float omega, bool scan)
 {
     const int lo = Mdl::INTERIOR_LINES ? 1 : 0;
     const int hi = (vertical ? ncols : nrows) - 1 - lo;
@@ -84,6 +118,10 @@ static int alr_lex_pass(hipStream_t s, const typename Mdl::Ctx *q, float *const 
     const size_t fs = (size_t)nrows * ncols;
     const int d = vertical ? 0 : 1;
     const size_t line_bytes = (size_t)n * sizeof(float4);
+    if (scan) {
+        if (vertical) return alr_scan_pass<Mdl, true>(s, q, x, f, order, nrows, ncols, nframes, lo, hi, omega);
+        return alr_scan_pass<Mdl, false>(s, q, x, f, order, nrows, ncols, nframes, lo, hi, omega);
+    }
     if (line_bytes > 160 * 1024) { // a line longer than LDS holds: the line buffer in global memory, one chain per launch
         float *g = nullptr;
         RC(ws_get(WS_LEX, line_bytes * nframes, &g));
@@ -345,20 +383,26 @@ static int run_alr(const char *who, hipStream_t s, const typename Mdl::Ctx *q, f
     RC(alr_make_twins(s, q, qt, nch, x, xt, nrows, ncols, nframes, &tw));
     AlrFactors f{};
     static const bool zebra1 = env_int("PDEIP_ALR_ZEBRA1", 0) != 0; // the one-lane-per-line kernel for every model (A/B timing)
-    if (mode == PDEIP_MODE_EXACT_ORDER || !zebra1) RC(alr_factor<Mdl>(s, q, qt, nch, nrows, ncols, nframes, &f));
+    const bool lex = mode != PDEIP_MODE_RED_BLACK; // the reference's line order: EXACT_ORDER and LINE_SCAN
+    // LINE_SCAN: a line's recurrences as scans (k_alr_scan); PDEIP_ALR_SCAN=0: the exact-order kernel everywhere
+    // A call whose longer lines k_alr_lex could not hold in LDS for all chains at once (two coupled fields beyond 5120 elements, any
+    // line beyond 10240) takes the exact-order kernels in both directions, as EXACT_ORDER does: bit-exact, hence inside the contract.
+    const size_t longest = (size_t)(nrows > ncols ? nrows : ncols) * sizeof(float4);
+    const bool scan = mode == PDEIP_MODE_LINE_SCAN && env_int("PDEIP_ALR_SCAN", 1) != 0 && nch == ALR_MODEL_CHAINS<Mdl> && nch * longest <= 160 * 1024;
+    if (lex || !zebra1) RC(alr_factor<Mdl>(s, q, qt, nch, nrows, ncols, nframes, &f));
     // zebra order, two coupled fields, factor planes present: one launch per colour for both fields (k_alr_zebra3_pair)
-    const bool pair = mode != PDEIP_MODE_EXACT_ORDER && nch == 2 && f.cp[0][0] != nullptr && f.cp[1][0] != nullptr && env_int("PDEIP_ALR_PAIR", 1) != 0;
+    const bool pair = !lex && nch == 2 && f.cp[0][0] != nullptr && f.cp[1][0] != nullptr && env_int("PDEIP_ALR_PAIR", 1) != 0;
     SweepTimer timer(s);
     for (int it = 0; it < iter; it++) {
-        if (mode == PDEIP_MODE_EXACT_ORDER)
-            RC(alr_lex_pass<Mdl>(s, q, x, f, fwd, nch, nrows, ncols, nframes, true, omega));
+        if (lex)
+            RC(alr_lex_pass<Mdl>(s, q, x, f, fwd, nch, nrows, ncols, nframes, true, omega, scan));
         else if (pair)
             RC(alr_zebra_pass_pair<Mdl>(s, q[0], x[0], f.cp[0][0], f.dv[0][0], q[1], x[1], f.cp[1][0], f.dv[1][0], nrows, ncols, nframes, true, omega));
         else
             for (int c = 0; c < nch; c++) RC(alr_zebra_pass<Mdl>(s, q[c], x[c], f.cp[c][0], f.dv[c][0], nrows, ncols, nframes, true, omega));
         RC(alr_transpose_many(s, xt, x, nch, nrows, ncols, nframes));
-        if (mode == PDEIP_MODE_EXACT_ORDER)
-            RC(alr_lex_pass<Mdl>(s, qt, xt, f, nch == 2 ? rev : fwd, nch, nrows, ncols, nframes, false, omega));
+        if (lex)
+            RC(alr_lex_pass<Mdl>(s, qt, xt, f, nch == 2 ? rev : fwd, nch, nrows, ncols, nframes, false, omega, scan));
         else if (pair)
             RC(alr_zebra_pass_pair<Mdl>(s, qt[1], xt[1], f.cp[1][1], f.dv[1][1], qt[0], xt[0], f.cp[0][1], f.dv[0][1], nrows, ncols, nframes, false, omega));
         else

@@ -94,6 +94,7 @@ int run_sweeps(hipStream_t s, SweepPlanes<Mdl> P, int nrows, int ncols, int nfra
     constexpr int NIT = Mdl::NIT;
     const size_t n = (size_t)nrows * ncols;
     tls.last_launches = 0;
+    if (mode == PDEIP_MODE_LINE_SCAN) mode = PDEIP_MODE_EXACT_ORDER; // LINE_SCAN only changes line relaxation
     if (dst != nullptr) {
         bool same = true;
         for (int f = 0; f < NIT; f++) same = same && dst[f] == P.it_out[f];

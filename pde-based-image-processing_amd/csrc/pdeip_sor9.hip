@@ -22,6 +22,7 @@ extern "C" int pdeip_pde_sor8_dev(void *stream, float *X, const float *TRACE, co
     const char *who = "pdeip_pde_sor8_dev";
     RC(check_dims(who, nrows, ncols, nframes));
     RC(check_mode(who, mode));
+    if (mode == PDEIP_MODE_LINE_SCAN) mode = PDEIP_MODE_EXACT_ORDER; // LINE_SCAN only changes line relaxation
     hipStream_t s = static_cast<hipStream_t>(stream);
     tls.last_launches = 0;
     if (iter <= 0) return PDEIP_OK;
