@@ -644,6 +644,57 @@ int pdeip_diffusion4(const float *Iin, int nrows, int ncols, int channels, const
 int pdeip_diffusion4_dev(void *stream, const float *Iin, int nrows, int ncols, int channels,
                          const pdeip_diffusion4_params *prm, float *Iout);
 
+/* ---- RANSAC surface fit (csrc/pdeip_ransac.hip) ---------------------------------------------------------------------------
+ * [M_out, Err] = SurfaceEquation(A, B, M_in, err_thr, min_set_size, iter) (mex/source/SurfaceEquation.c + library/ransac.c): the
+ * RANSAC fit of A * M = B, A single [ndata x ncoef] column-major with ncoef = 3 ([X Y 1]) or 6 ([X^2 Y^2 XY X Y 1]), B [ndata];
+ * n = ncoef + 1 samples per hypothesis.  The control flow is RANSAC()'s (ransac.c:31-220): err_thr2 = err_thr*err_thr in single;
+ * abs_min = (unsigned)(min_set_size*(float)ndata + 0.5f) (a value below 1, negative included, gives 0); a row is an inlier iff
+ * e <= err_thr2 (a NaN error never is).  A given model M_in (NULL: none) is scored first: it seeds the best error sum and is licit
+ * iff its inliers >= abs_min.  Then hypotheses 0..iter-1 IN ORDER: one becomes the best model iff inliers >= abs_min && sum <
+ * best sum (strict: the earliest wins a tie); otherwise, while no licit model exists yet, it replaces the best-inlier model iff
+ * inliers >= the best-inlier count (not strict: the latest wins).  M_out is the best licit model, else the best-inlier model;
+ * err_out [ndata] holds its errors.  Where the reference is undefined or not deterministic, this library's definitions:
+ *   samples      sets [iter x n] 0-based row indices, hypothesis-major (duplicates allowed), or, with sets == NULL, drawn from
+ *                seed: sample k of hypothesis i is (uint32)(((splitmix64(seed + i*n + k) >> 32) * (uint64)ndata) >> 32), where
+ *                splitmix64(x) is { z = x + 0x9E3779B97F4A7C15; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) *
+ *                0x94D049BB133111EB; return z ^ (z >> 31); } in 64-bit wrapping arithmetic (the reference: rand() % ndata).
+ *   fit          (the reference: sgels) Householder QR in float64 on the samples widened from single, no pivoting, every sum in
+ *                ascending index, no FMA, correctly rounded sqrt and division; for column k: s = sum_{i>=k} R[i][k]^2, norm =
+ *                sqrt(s), alpha = R[k][k] > 0 ? -norm : norm, v_k = R[k][k] - alpha, v_i = R[i][k], vtv = sum v_i^2, then for
+ *                every later column c and at last the right-hand side f = (2*sum v_i*c_i)/vtv, c_i = c_i - f*v_i, and R[k][k] =
+ *                alpha; back-substitution t = b[k], t = t - R[k][j]*x[j] for j = k+1.., x[k] = t/R[k][k]; x rounded to single.  An
+ *                exactly zero norm marks the hypothesis singular: its model is zero and all its errors are FLT_MAX
+ *                (SurfaceEquation.c:417-421).
+ *   error        of row j for model m, in single without FMA: t = A[j,0]*m[0]; t = t + A[j,1]*m[1]; ...; d = t - B[j]; e = d*d
+ *                (the reference: sgemm, whose order is unspecified).
+ *   score        the inlier count is exact; the error sum over the inliers is float64, reduced in a fixed order that does not
+ *                depend on the hypothesis (no floating-point atomics): equal models get equal sums, two calls the same bits.
+ *   no model     iter <= 0 and no licit given model: the given model and its errors; with M_in == NULL: PDEIP_ERR_ARG (the
+ *                reference returns uninitialised memory).
+ * inliers_out (NULL ok) [iter + 1]: [0] the given model's count (-1 if none), [1 + i] hypothesis i's; errsum_out (NULL ok)
+ * [iter + 1] the float64 sums likewise ([0] = 0 if none).  Refused with PDEIP_ERR_ARG before any HIP call: a NULL A, B, M_out or
+ * err_out, ncoef not 3 or 6, ndata < 1, a non-finite err_thr or min_set_size, and in the host form a sets entry >= ndata.
+ * pdeip_set_mode does not apply.  Parity with the reference's compiled gateway is unpinned (it needs MATLAB's BLAS and LAPACK). */
+int pdeip_surface_equation(const float *A, const float *B, int ndata, int ncoef, const float *M_in, float err_thr,
+                           float min_set_size, int iter, const unsigned *sets, unsigned long long seed, float *M_out, float *err_out,
+                           int *inliers_out, double *errsum_out);
+/* The same on device pointers (sets, inliers_out and errsum_out too), asynchronous on `stream`: workspace from the library's
+ * cache, one stream, no host read-back, no graph branches (graph-capturable).  A sets entry >= ndata cannot be refused here: it
+ * makes its hypothesis singular and nothing is read through it. */
+int pdeip_surface_equation_dev(void *stream, const float *A, const float *B, int ndata, int ncoef, const float *M_in, float err_thr,
+                               float min_set_size, int iter, const unsigned *sets, unsigned long long seed, float *M_out,
+                               float *err_out, int *inliers_out, double *errsum_out);
+/* The fit as the segmentation drivers use it (DispSegmentation.m:329-360), resident: the data are the pixels with PHI >= 0 (a NaN
+ * PHI is false) of the [nrows x ncols] planes PHI and D, ranked in column-major order; pixel (i, j) (0-based) has X = j + 1, Y =
+ * i + 1, the row [X Y 1] (order 1) or [X^2 Y^2 XY X Y 1] (order 2) with each product formed in double and rounded to single, and
+ * B = D(i, j).  The result equals pdeip_surface_equation_dev on that A, B bit for bit; ndata, abs_min and the seeded draws are
+ * formed on the device.  M_out [3 | 6]; dist_out (NULL ok) [nrows x ncols]: the error formula on EVERY pixel's row against D
+ * (distD of :349/:360, in single; FLT_MAX everywhere when the chosen hypothesis is singular); ndata_out (device, NULL ok): the number of pixels taken.  A mask without pixels sets *ndata_out
+ * = 0 and M_out = M_in (NaN when none was given).  Same refusals, with `order` not 1 or 2 in place of ncoef. */
+int pdeip_surface_fit_masked_dev(void *stream, const float *PHI, const float *D, int nrows, int ncols, int order, const float *M_in,
+                                 float err_thr, float min_set_size, int iter, const unsigned *sets, unsigned long long seed,
+                                 float *M_out, float *dist_out, int *ndata_out);
+
 #ifdef __cplusplus
 }
 #endif

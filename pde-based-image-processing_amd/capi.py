@@ -133,6 +133,10 @@ SIGNATURES = {
     # nonlinear diffusion (csrc/pdeip_diffusion.hip)
     "pdeip_diffusion4": [_P, _I, _I, _I, _P, _P],
     "pdeip_diffusion4_dev": [_P, _P, _I, _I, _I, _P, _P],
+    # RANSAC surface fit (csrc/pdeip_ransac.hip)
+    "pdeip_surface_equation": [_P, _P, _I, _I, _P, _F, _F, _I, _P, ctypes.c_ulonglong, _P, _P, _P, _P],
+    "pdeip_surface_equation_dev": [_P, _P, _P, _I, _I, _P, _F, _F, _I, _P, ctypes.c_ulonglong, _P, _P, _P, _P],
+    "pdeip_surface_fit_masked_dev": [_P, _P, _P, _I, _I, _I, _P, _F, _F, _I, _P, ctypes.c_ulonglong, _P, _P, _P],
     # library state
     "pdeip_set_mode": [_I],
     "pdeip_get_mode": [],

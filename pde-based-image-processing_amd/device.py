@@ -223,6 +223,26 @@ def cv_terms(PHI, c0, c1, dh_floor, DH_out, G_out):
               DH_out.data_ptr(), G_out.data_ptr())
 
 
+def surface_fit_masked(PHI, D, order, M_in, err_thr, min_set_size, iter, M_out, dist_out=None, ndata_out=None, seed=0, sets=None):
+    """The RANSAC surface fit on the pixels with PHI >= 0 (pdeip_surface_fit_masked_dev): PHI, D planes [ncols, nrows]; order 1 | 2;
+    M_in float32 [3 | 6] tensor or None; M_out float32 [3 | 6]; dist_out a plane or None; ndata_out an int32 tensor of one element
+    or None; sets an int32 tensor [iter, ncoef + 1] of 0-based ranks or None (then drawn from seed).  Nothing is read back."""
+    _chk(PHI, D, M_out, *[t for t in (M_in, dist_out) if t is not None])
+    if D.shape != PHI.shape or PHI.dim() != 2 or (dist_out is not None and dist_out.shape != PHI.shape):
+        raise capi.PdeipError(capi.PDEIP_ERR_ARG, "surface_fit_masked: PHI, D and dist_out must be planes of one size")
+    ncoef = 3 if order == 1 else 6
+    if M_out.numel() != ncoef or (M_in is not None and M_in.numel() != ncoef):
+        raise capi.PdeipError(capi.PDEIP_ERR_ARG, "surface_fit_masked: M_in and M_out must have %d elements" % ncoef)
+    for t, n in ((ndata_out, 1), (sets, max(int(iter), 0) * (ncoef + 1))):
+        if t is not None and (t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous() or t.numel() != n):
+            raise capi.PdeipError(capi.PDEIP_ERR_ARG, "surface_fit_masked: ndata_out / sets must be contiguous int32 CUDA tensors of 1 / iter*(ncoef+1) elements")
+    nrows, ncols, _ = _dims(PHI)
+    opt = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    capi.call("pdeip_surface_fit_masked_dev", _stream(), PHI.data_ptr(), D.data_ptr(), nrows, ncols, int(order), opt(M_in), float(err_thr),
+              float(min_set_size), int(iter), opt(sets), ctypes.c_ulonglong(int(seed) & ((1 << 64) - 1)), M_out.data_ptr(), opt(dist_out),
+              opt(ndata_out))
+
+
 class Diffusion4Params(ctypes.Structure):
     """pdeip_diffusion4_params: NaN keeps the driver's default (alpha 25, outer_iter 5)."""
     _fields_ = [("alpha", ctypes.c_double), ("outer_iter", ctypes.c_double)]

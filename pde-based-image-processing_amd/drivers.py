@@ -509,3 +509,22 @@ def Diffusion4_v10(I_in, as_single=False, **param):
     capi.call("pdeip_diffusion4", I.ctypes.data, I.shape[0], I.shape[1], I.shape[2] if I.ndim == 3 else 1, ctypes.addressof(prm),
               out.ctypes.data)
     return out if as_single else uint8_matlab(out)
+
+
+def SurfaceEquation(A, B, M_in, err_thr, min_set_size, iter, seed=None, sets=None):
+    """[M_out, Err] = SurfaceEquation(A, B, M_in, err_thr, min_set_size, iter) (mex/source/SurfaceEquation.c): the RANSAC fit of a
+    first- ([X Y 1]) or second-order ([X^2 Y^2 XY X Y 1]) polynomial surface in one pdeip_surface_equation call.  Arguments in any
+    numeric type, taken as single; M_in None or empty: none.  seed / sets choose the samples (include/pdeip.h); without either a
+    seed is drawn from the clock once and advanced per call.  Returns M_out [ncoef, 1] and Err [ndata, 1] as the gateway does."""
+    from . import mex_api
+
+    A = np.asarray(A, dtype=np.float32)
+    B = np.asarray(B, dtype=np.float32).reshape(-1)
+    if A.ndim != 2 or A.shape[0] != B.size:
+        raise ValueError("SurfaceEquation: A is %s but B has %d elements" % (A.shape, B.size))
+    if M_in is not None and np.size(M_in) == 0:
+        M_in = None
+    if M_in is not None and np.size(M_in) != A.shape[1]:
+        raise ValueError("SurfaceEquation: M_in must have as many elements as A has columns")
+    M, err, _, _ = mex_api.surface_equation(A, B, M_in, float(np.float32(err_thr)), float(np.float32(min_set_size)), int(iter), seed, sets)
+    return np.asfortranarray(M.reshape(-1, 1)), np.asfortranarray(err.reshape(-1, 1))

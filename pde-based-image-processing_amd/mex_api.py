@@ -11,7 +11,8 @@ All arithmetic happens in libpdeip.so on the GPU; this file only checks, packs a
 
 Reference: Oflow_sor_elin4_2d.c, Oflow_sor_llin4_2d.c, Oflow_sor_llin8_2d.c, Oflow_lhs_elin4_2d.c,
 Oflow_lhs_llin4_2d.c, Disp_sor_llin4_2d.c, PDEsolver4.c, PDEsolver8.c, DdiffWeights.c,
-BilinInterp_2d.c, FstDerivatives5.c, SndDerivatives5.c, AC_solver_2d.c, Reinit.c, CV_solver_2d.c (all under mex/source/).
+BilinInterp_2d.c, FstDerivatives5.c, SndDerivatives5.c, AC_solver_2d.c, Reinit.c, CV_solver_2d.c, SurfaceEquation.c (all under
+mex/source/).
 """
 import numpy as np
 
@@ -301,6 +302,62 @@ def Reinit(PHI, T, nargout=1):
     nrows, ncols = PHI.shape[:2]
     _run("pdeip_reinit", _ptr(PHI), nrows, ncols, _frames(PHI), T, _ptr(out))
     return out
+
+
+_surface_seed = None  # the stub's rule: drawn from the clock on the first unseeded call, advanced per call
+
+
+def surface_equation(A, B, M_in, err_thr, min_set_size, iter, seed=None, sets=None):
+    """pdeip_surface_equation on numpy arrays: (M_out [ncoef], Err [ndata], inliers [iter+1], errsum [iter+1]).  A single
+    [ndata, ncoef] (column-major), B [ndata], M_in [ncoef] or None, sets uint32 [iter, ncoef+1] or None (then drawn from seed)."""
+    global _surface_seed
+    import ctypes
+    import time
+
+    A = np.asfortranarray(A, dtype=np.float32)
+    B = np.ascontiguousarray(B, dtype=np.float32).reshape(-1)
+    ndata, ncoef = A.shape
+    it = max(int(iter), 0)
+    M_in = None if M_in is None else np.ascontiguousarray(M_in, dtype=np.float32).reshape(-1)
+    if sets is not None:
+        sets = np.ascontiguousarray(sets, dtype=np.uint32)
+        if sets.size != it * (ncoef + 1):
+            raise MexError(capi.PDEIP_ERR_ARG, "SurfaceEquation: 'sets' must hold iter x (ncoef + 1) indices")
+    elif seed is None:
+        if _surface_seed is None:
+            _surface_seed = int(time.time())
+        seed, _surface_seed = _surface_seed, (_surface_seed + 0x9E3779B97F4A7C15) & ((1 << 64) - 1)
+    M = np.zeros(ncoef, np.float32)
+    err = np.zeros(ndata, np.float32)
+    inl = np.zeros(it + 1, np.int32)
+    esum = np.zeros(it + 1, np.float64)
+    _run("pdeip_surface_equation", _ptr(A), _ptr(B), ndata, ncoef, _ptr(M_in), float(err_thr), float(min_set_size), int(iter), _ptr(sets),
+         ctypes.c_ulonglong(int(seed or 0) & ((1 << 64) - 1)), _ptr(M), _ptr(err), _ptr(inl), _ptr(esum))
+    return M, err, inl, esum
+
+
+def SurfaceEquation(A_in, B_in, M_in, err_thr, min_set_size, iter, seed=None, sets=None, nargout=2):
+    """[M_out, Err] = SurfaceEquation(A_in,B_in,M_in,err_thr,min_set_size,iter)  -- mex/source/SurfaceEquation.c:69-220.  An empty
+    M_in means none; seed / sets: the samples (pdeip.h), without either a seed drawn from the clock once and advanced per call."""
+    who = "SurfaceEquation error"
+    A = _single("A_in", who, A_in)
+    B = _single("B_in", who, B_in)
+    M = _single("M_in", who, M_in)
+    err_thr, min_set_size = _scalar("err_thr", who, err_thr), _scalar("min_set_size", who, min_set_size)
+    iter = _scalar("iter", who, iter)
+    if A.ndim != 2 or B.ndim != 2:
+        raise MexError(capi.PDEIP_ERR_ARG, "SurfaceEquation error: 'A_in' and 'B_in' must be matrices.")
+    if M.size and A.shape[1] != M.shape[0]:
+        raise MexError(capi.PDEIP_ERR_ARG, "SurfaceEquation error: M_in is a column vector with as many row elements as A_in has columns!")
+    if A.shape[0] != B.shape[0]:
+        raise MexError(capi.PDEIP_ERR_ARG, "SurfaceEquation error: A_in and B_in have to have same amount of rows!")
+    if A.shape[1] not in (3, 6):
+        raise MexError(capi.PDEIP_ERR_ARG, "SurfaceEquation error: only 1st and 2nd order polynomials are implemented!")
+    if nargout < 2:
+        raise MexError(capi.PDEIP_ERR_ARG, "SurfaceEquation error: insufficient number of outputs. Outputs from this function is 'M_out' and 'error_out'")
+    it = int(iter) if iter > 0 else 0  # (unsigned int)iter of the gateway, without its wrap-around for a negative iter
+    Mo, err, _, _ = surface_equation(A, B[:, 0], M[:, 0] if M.size else None, err_thr, min_set_size, it, seed, sets)
+    return np.asfortranarray(Mo.reshape(-1, 1)), np.asfortranarray(err.reshape(-1, 1))
 
 
 def set_mode(mode):
