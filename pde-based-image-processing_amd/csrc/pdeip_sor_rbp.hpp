@@ -26,6 +26,7 @@
 // Halo.  A half-sweep invalidates one halo row and one halo column per side: 2S columns per side are loaded
 // and 8 rows (two lanes) per side are recomputed, so a wave owns 240 rows; redundancy (TJ + 4S)/TJ x 256/240.
 #pragma once
+#include <type_traits>
 #include "pdeip_sor_rb.hpp"
 
 namespace pdeip {
@@ -144,6 +145,13 @@ __device__ __forceinline__ void rbp_barrier() { asm volatile("" ::: "memory"); }
 #else
 __device__ __forceinline__ void rbp_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 #endif
+// Two more timing experiments (results are garbage; never in the product), which price the two sides of a step apart:
+//   RBP_LOADER_ONLY  the sweep waves only attend the barriers of their march: the launch takes what the loader's stream takes;
+//   RBP_SWEEPS_ONLY  the loader only attends the barriers: the sweep waves march, unchanged, over whatever LDS holds, global
+//                    stores included: the launch takes what the sweep waves' own chain takes.
+#if defined(RBP_LOADER_ONLY) && defined(RBP_SWEEPS_ONLY)
+#error "RBP_LOADER_ONLY and RBP_SWEEPS_ONLY price one side each: not both"
+#endif
 
 // One colour of one column, branch-free, for the fields [F0, F0+NF) of the model: OUT <- CEN with elements {E0, E0+2}
 // relaxed where the row is an interior pixel (ok[], fixed per lane for the whole march).  XC holds the centre values of ALL
@@ -202,14 +210,26 @@ __device__ __forceinline__ void rbp_phase(float (&OUT)[NF][4], const float (&C)[
     }
 }
 
-// The march of one sweep wave: sweep s of the launch, fields [F0, F0+NF) of the model.
-template <class Mdl, int S, bool FIRST, int F0, int NF>
+// The march of one sweep wave: sweep s of the launch, fields [F0, F0+NF) of the model.  Two roles are fixed at compile time, so
+// that a wave carries neither the code nor the live registers of a role it does not play:
+//   DERIVE    sweep 0 of a call's first launch, which builds the divisor planes as it goes (s is 0 then);
+//   INTERIOR  every one of the wave's 256 rows is an interior row of the image (1 .. nrows-2): nothing to mask, no border row
+//             to replicate.
+// The march itself is a lead-in, a steady state and a lead-out.  In the steady state neither half-sweep touches a border
+// column and the colour of column x alternates, so six steps (three window rotations x two colours) make one trip without a
+// test of x or of the colour; the lead-in and the lead-out run the general step.
+template <class Mdl, int S, int F0, int NF, bool DERIVE, bool INTERIOR>
 __device__ __forceinline__ void rbp_sweep_wave(const SweepPlanes<Mdl> &P, float *dout0, float *dout1, float *Kring, float *Qring, float *Oring, float *Hring,
-                                               int s, int lane, int r, int nrows, int ncols, int j0, int j1, int xbase, int nsteps,
+                                               int s_wave, int lane, int r, int nrows, int ncols, int j0, int j1, int xbase, int nsteps,
                                                float omega, int col0, size_t fo, int mirror)
 {
+    const int s = DERIVE ? 0 : s_wave;
     using L = RbpLayout<Mdl, S>;
     constexpr int NIT = L::NIT, NRO = L::NRO, NRO1 = at_least_one<NRO>::value, NCF = L::NCF, COL = L::COL;
+#ifdef RBP_LOADER_ONLY
+    for (int t = 0; t <= nsteps; t++) rbp_barrier(); // the meeting in front of step 0 and one per step
+    return;
+#endif
     const float om1 = 1.0f - omega;
     const bool store_lane = (lane >= 2) && (lane <= 61);
     auto inner = [&](int col) { return col >= 1 && col <= ncols - 2; };
@@ -218,8 +238,8 @@ __device__ __forceinline__ void rbp_sweep_wave(const SweepPlanes<Mdl> &P, float 
     // the lane holds the top / bottom border row (nrows is a multiple of 4 here, so they are elements 0 and 3)
     bool ok[4];
 #pragma unroll
-    for (int e = 0; e < 4; e++) ok[e] = (r + e >= 1) && (r + e <= nrows - 2);
-    const bool top_lane = (r == 0), bot_lane = (r == nrows - 4);
+    for (int e = 0; e < 4; e++) ok[e] = INTERIOR || ((r + e >= 1) && (r + e <= nrows - 2));
+    const bool top_lane = !INTERIOR && (r == 0), bot_lane = !INTERIOR && (r == nrows - 4);
 
     // Three-column windows.  The step below is instantiated three times with the roles rotated, so no window ever moves:
     // O*: the previous sweep's result at x-1, x, x+1, ALL fields (centre values of the other fields feed the coupling term);
@@ -245,19 +265,29 @@ __device__ __forceinline__ void rbp_sweep_wave(const SweepPlanes<Mdl> &P, float 
     }
     // ring positions: K ring slot of column x (group x - xbase - 1 = t - 3s - 1; a wave that is still in front of the first
     // fetched column reads some slot whose content it never uses), O ring slot of column x+1 (sweep 0), H ring parity
-    int ki = ((-3 * s - 1) % L::NK + L::NK) % L::NK, qi = ((-3 * s) % L::NQ + L::NQ) % L::NQ, oi = 0, hp = 1;
+    // Kept as float offsets into the rings, each advanced by one column and wrapped with one compare per step.  The column a
+    // wave takes in comes from the O ring (sweep 0: NO slots) or from its predecessor's pair of H slots, the column it hands
+    // on goes to its own pair: one ring base and one wrap length per wave, chosen here and not in the step.
+    constexpr int KCOL = NCF * COL, QCOL = NRO * COL, ICOL = NIT * COL;
+    int koff = (((-3 * s - 1) % L::NK + L::NK) % L::NK) * KCOL, qoff = (((-3 * s) % L::NQ + L::NQ) % L::NQ) * QCOL;
+    const float *const in_ring = (s == 0) ? Oring : Hring + (size_t)(s - 1) * 2 * ICOL;
+    const int in_wrap = (s == 0 ? L::NO : 2) * ICOL;
+    int in_off = (s == 0) ? 0 : ICOL, out_off = 0;
+    float *const out_ring = Hring + (size_t)(s < S - 1 ? s : 0) * 2 * ICOL; // written by sweeps 0 .. S-2 only
 
-    auto step = [&](int t, float (&Om)[NIT][4], float (&Oc)[NIT][4], float (&Op)[NIT][4], float (&Rpp)[NF][4], float (&Rp)[NF][4],
+    // MODE 0 / 1: a steady-state step whose red column has that colour; MODE 2: any step
+    auto step = [&](int t, auto mode_c, float (&Om)[NIT][4], float (&Oc)[NIT][4], float (&Op)[NIT][4], float (&Rpp)[NF][4], float (&Rp)[NF][4],
                     float (&Rc)[NF][4], const float (&Kp)[NCF][4], float (&Kc)[NCF][4], float (&Kn)[NCF][4]) __attribute__((always_inline)) {
+        constexpr int MODE = decltype(mode_c)::value;
         const int x = xbase + t - 3 * s; // this wave's red column; black on x-1
 #ifdef PDEIP_RBP_STAMPS
         const bool stamp_on = (blockIdx.x == 100) && (s == RBP_STAMP_SWEEP) && (F0 == 0) && (t >= RBP_STAMP_T0) && (t < RBP_STAMP_T0 + 24);
 #endif
         RBP_STAMP(0);
         // ---- take in column x+1 of the previous sweep's result, and the coefficients of columns x and x-1 ----
-        float *const ks = Kring + (size_t)ki * NCF * COL; // slot of column x (Kc, read one step ago -- before the loop for step 0; column x-1 is Kp)
+        float *const ks = Kring + koff; // slot of column x (Kc, read one step ago -- before the loop for step 0; column x-1 is Kp)
         {
-            const float *src = (s == 0) ? Oring + (size_t)oi * NIT * COL : Hring + (size_t)((s - 1) * 2 + hp) * NIT * COL;
+            const float *src = in_ring + in_off;
 #pragma unroll
             for (int f = 0; f < NIT; f++) rbp_lds_read(Op[f], src + f * COL, lane);
 #pragma unroll
@@ -270,16 +300,16 @@ __device__ __forceinline__ void rbp_sweep_wave(const SweepPlanes<Mdl> &P, float 
                         Q0[f][e] = Qn[f][e];
                     }
                     // read-only fields ride one column ahead of the coefficients (the red half reads them at x+1)
-                    rbp_lds_read(Qn[f], Qring + ((size_t)qi * NRO + (NRO > 0 ? f : 0)) * COL, lane);
+                    rbp_lds_read(Qn[f], Qring + qoff + (NRO > 0 ? f : 0) * COL, lane);
                 }
         }
-        const int p = (x + col0) & 1;
+        const int p = MODE < 2 ? MODE : (x + col0) & 1;
 #ifdef PDEIP_RBP_STAMPS
         if (stamp_on) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #endif
         RBP_STAMP(1); // the step's LDS reads have landed
 
-        if (FIRST && s == 0) {
+        if (DERIVE) {
             // Sweep 1 of a call builds the divisor planes as it goes (opticalflowSolvers.c:111-127): column x was just read
             // raw; derive it, put the derived planes back into its K-ring slot (this wave reads them again as column x-1 in the
             // next step, the later sweeps three steps from now) and store them if launches follow that need them.  A wave
@@ -362,32 +392,29 @@ __device__ __forceinline__ void rbp_sweep_wave(const SweepPlanes<Mdl> &P, float 
         // Coefficients of column x+1, for the next step: read BETWEEN the two half-sweeps.  At the top of the step they sat between
         // the barrier and the first multiply (the compiler waits for every outstanding LDS read there); behind both half-sweeps they
         // sat in front of the hand-off write, whose acknowledgement the barrier waits for.  Here the black half hides them.
+        const int knext = (koff + KCOL == L::NK * KCOL) ? 0 : koff + KCOL;
         auto read_next_coefficients = [&]() __attribute__((always_inline)) {
-            const float *kn = Kring + (size_t)(ki + 1 == L::NK ? 0 : ki + 1) * NCF * COL;
+            const float *kn = Kring + knext;
 #pragma unroll
             for (int f = 0; f < NCF; f++) rbp_lds_read(Kn[f], kn + f * COL, lane);
         };
         const int xb = x - 1;
         float F[NF][4];
-        if (x >= 3 && x <= ncols - 3) {
-            // ---- the common case: neither half-sweep touches or reads a border column; one parity branch for both ----
+        if constexpr (MODE < 2) {
+            // ---- the steady state (3 <= x <= ncols - 3): neither half-sweep touches or reads a border column ----
             // red on column x: Rc <- Oc with the red pixels relaxed; black on column x-1: F <- Rp with the black pixels relaxed
             // (the other fields' centre values at the black pixels are still the previous sweep's: the red half left them alone)
-            if (p == 0) {
-                rbp_phase<Mdl, F0, NF, 0>(Rc, OcF, OmF, OpF, Oc, Q0, Q1, Qn, Kc, ok, omega, om1);
-                read_next_coefficients();
-                rbp_phase<Mdl, F0, NF, 0>(F, Rp, Rpp, Rc, Om, Q1, Q2, Q0, Kp, ok, omega, om1);
-            } else {
-                rbp_phase<Mdl, F0, NF, 1>(Rc, OcF, OmF, OpF, Oc, Q0, Q1, Qn, Kc, ok, omega, om1);
-                read_next_coefficients();
-                rbp_phase<Mdl, F0, NF, 1>(F, Rp, Rpp, Rc, Om, Q1, Q2, Q0, Kp, ok, omega, om1);
-            }
+            rbp_phase<Mdl, F0, NF, MODE>(Rc, OcF, OmF, OpF, Oc, Q0, Q1, Qn, Kc, ok, omega, om1);
+            read_next_coefficients();
+            rbp_phase<Mdl, F0, NF, MODE>(F, Rp, Rpp, Rc, Om, Q1, Q2, Q0, Kp, ok, omega, om1);
+            if (!INTERIOR) {
 #pragma unroll
-            for (int f = 0; f < NF; f++) { // rows first (:161-170): border row 0 <- row 1, border row nrows-1 <- row nrows-2
-                rbp_replicate_rows(F[f], top_lane, bot_lane);
+                for (int f = 0; f < NF; f++) { // rows first (:161-170): border row 0 <- row 1, border row nrows-1 <- row nrows-2
+                    rbp_replicate_rows(F[f], top_lane, bot_lane);
+                }
             }
         } else {
-            // ---- columns at the image border (and the clamped columns outside it) ----
+            // ---- any column: those at the image border and the clamped ones outside it; an inner column comes out as above ----
             read_next_coefficients();
             if (inner(x)) {
                 // sweeps after the first see a border column as the replicate of its inner neighbour after the previous sweep
@@ -420,9 +447,11 @@ __device__ __forceinline__ void rbp_sweep_wave(const SweepPlanes<Mdl> &P, float 
                         Ev[f][e] = eb ? OmF[f][e] : Rc[f][e];
                     }
                 PDEIP_RBP_PHASE(F, Rp, Wv, Ev, Om, Q1, Q2, Q0, Kp);
+                if (!INTERIOR) {
 #pragma unroll
-                for (int f = 0; f < NF; f++) {
-                    rbp_replicate_rows(F[f], top_lane, bot_lane);
+                    for (int f = 0; f < NF; f++) {
+                        rbp_replicate_rows(F[f], top_lane, bot_lane);
+                    }
                 }
             } else {
 #pragma unroll
@@ -434,22 +463,24 @@ __device__ __forceinline__ void rbp_sweep_wave(const SweepPlanes<Mdl> &P, float 
 #undef PDEIP_RBP_PHASE
         RBP_STAMP(2); // both half-sweeps issued
         if (s < S - 1) {
-            float *dst = Hring + (size_t)(s * 2 + (hp ^ 1)) * NIT * COL;
+            float *dst = out_ring + out_off;
 #pragma unroll
             for (int f = 0; f < NF; f++) rbp_lds_write(dst + (F0 + f) * COL, lane, F[f]);
-        } else if (store_lane && xb >= j0 && xb < j1 && inner(xb)) {
+        } else if (store_lane && xb >= j0 && xb < j1 && (MODE < 2 || inner(xb))) {
 #pragma unroll
             for (int f = 0; f < NF; f++) {
                 float *out = P.it_out[F0 + f] + fo;
                 rb_store4<true>(F[f], out, cmap(xb), r, nrows);
-                if (xb == 1) rb_store4<true>(F[f], out, cmap(0), r, nrows); // then columns (:172-179)
-                if (xb == ncols - 2) rb_store4<true>(F[f], out, cmap(ncols - 1), r, nrows);
+                if (MODE == 2) { // the steady state has 2 <= xb <= ncols - 4
+                    if (xb == 1) rb_store4<true>(F[f], out, cmap(0), r, nrows); // then columns (:172-179)
+                    if (xb == ncols - 2) rb_store4<true>(F[f], out, cmap(ncols - 1), r, nrows);
+                }
             }
         }
-        ki = (ki + 1 == L::NK) ? 0 : ki + 1;
-        qi = (qi + 1 == L::NQ) ? 0 : qi + 1;
-        oi = (oi + 1 == L::NO) ? 0 : oi + 1;
-        hp ^= 1;
+        koff = knext;
+        if (NRO > 0) qoff = (qoff + QCOL == L::NQ * QCOL) ? 0 : qoff + QCOL;
+        in_off = (in_off + ICOL == in_wrap) ? 0 : in_off + ICOL;
+        out_off ^= ICOL;
         RBP_STAMP(3); // hand-off written / stores issued, bookkeeping done
 #ifdef PDEIP_RBP_STAMPS
         if (stamp_on) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -461,12 +492,45 @@ __device__ __forceinline__ void rbp_sweep_wave(const SweepPlanes<Mdl> &P, float 
 
     rbp_barrier(); // group 0 is in LDS
 #pragma unroll
-    for (int f = 0; f < NCF; f++) rbp_lds_read(KB[f], Kring + ((size_t)ki * NCF + f) * COL, lane); // "column x" of step 0
-    // the O/R windows and the coefficient triple (columns x-1, x, x+1) rotate with period 3: three steps per trip
-    for (int t = 0; t < nsteps; t += 3) {
-        step(t, O0, O1, O2, R0, R1, R2, KA, KB, KC);
-        if (t + 1 < nsteps) step(t + 1, O1, O2, O0, R1, R2, R0, KB, KC, KA);
-        if (t + 2 < nsteps) step(t + 2, O2, O0, O1, R2, R0, R1, KC, KA, KB);
+    for (int f = 0; f < NCF; f++) rbp_lds_read(KB[f], Kring + koff + f * COL, lane); // "column x" of step 0
+    // The steady state: the steps [tA, tB) in which 3 <= x <= ncols - 3, cut to whole trips of six that begin on window rotation 0
+    // (tA a multiple of 3) with a red column of colour 0; what the cut leaves over goes to the lead-in and the lead-out.
+    int tA = 0, tB = 0;
+    {
+        const int lo = 3 - xbase + 3 * s > 0 ? 3 - xbase + 3 * s : 0;
+        const int hi = ncols - 3 - xbase + 3 * s < nsteps - 1 ? ncols - 3 - xbase + 3 * s : nsteps - 1; // the last such step
+        int ta = (lo + 2) / 3 * 3;
+        if ((xbase + ta - 3 * s + col0) & 1) ta += 3;
+        if (hi + 1 - ta >= 6) {
+            tA = ta;
+            tB = ta + (hi + 1 - ta) / 6 * 6;
+        }
+    }
+    using M0 = std::integral_constant<int, 0>;
+    using M1 = std::integral_constant<int, 1>;
+    using M2 = std::integral_constant<int, 2>;
+    // the O/R windows and the coefficient triple (columns x-1, x, x+1) rotate with period 3: three steps per trip of the general march
+    int t = 0;
+#pragma unroll 1
+    for (int part = 0; part < 2; part++) { // lead-in and lead-out: one copy of the general step's code for both
+        const int t1 = part == 0 ? tA : nsteps;
+#pragma unroll 1
+        for (; t < t1; t += 3) {
+            step(t, M2(), O0, O1, O2, R0, R1, R2, KA, KB, KC);
+            if (t + 1 < t1) step(t + 1, M2(), O1, O2, O0, R1, R2, R0, KB, KC, KA);
+            if (t + 2 < t1) step(t + 2, M2(), O2, O0, O1, R2, R0, R1, KC, KA, KB);
+        }
+        if (part == 0) {
+#pragma unroll 1
+            for (; t < tB; t += 6) {
+                step(t, M0(), O0, O1, O2, R0, R1, R2, KA, KB, KC);
+                step(t + 1, M1(), O1, O2, O0, R1, R2, R0, KB, KC, KA);
+                step(t + 2, M0(), O2, O0, O1, R2, R0, R1, KC, KA, KB);
+                step(t + 3, M1(), O0, O1, O2, R0, R1, R2, KA, KB, KC);
+                step(t + 4, M0(), O1, O2, O0, R1, R2, R0, KB, KC, KA);
+                step(t + 5, M1(), O2, O0, O1, R2, R0, R1, KC, KA, KB);
+            }
+        }
     }
 }
 
@@ -529,6 +593,10 @@ k_sor_rbp(SweepPlanes<Mdl> P, float *dout0, float *dout1, int nrows, int ncols, 
         // group g = column xbase + 1 + g, consumed by sweep 0 in step g
         const int lw = wave - S * NW; // which loader
         const int rr = r < 0 ? 0 : (r > nrows - 4 ? nrows - 4 : r);
+#ifdef RBP_SWEEPS_ONLY
+        for (int t = 0; t <= nsteps; t++) rbp_barrier(); // the meeting in front of step 0 and one per step
+        return;
+#endif
         int kslot = 0, qslot = 0, oslot = 0;
         auto issue = [&](int g) __attribute__((always_inline)) {
             const int y = xbase + 1 + g;
@@ -570,7 +638,10 @@ k_sor_rbp(SweepPlanes<Mdl> P, float *dout0, float *dout1, int nrows, int ncols, 
 #endif
             RBP_STAMP(0);
             if (RBP_LOADER_SLEEP > 0) __builtin_amdgcn_s_sleep(RBP_LOADER_SLEEP);
-            if (t + L::P < nsteps) { // group nsteps-1 is the last one a sweep wave reads (as "column x+1" of its last step)
+            // The last column a unit stores, j1-1, depends through S sweeps of two half-sweeps on input column j1-1+2S: group
+            // TJ+4S-1 = nsteps-S.  The S-1 groups behind it are read (the waves march on over stale ring slots) but reach no
+            // stored pixel: not fetched.
+            if (t + L::P <= nsteps - S) {
                 issue(t + L::P);
                 RBP_STAMP(1); // the step's DMA instructions issued
                 landed(); // group t+1 has landed
@@ -597,17 +668,33 @@ k_sor_rbp(SweepPlanes<Mdl> P, float *dout0, float *dout1, int nrows, int ncols, 
 #ifndef RBP_ROLE_REMAP
 #define RBP_ROLE_REMAP 1
 #endif
+    // The wave's role, chosen once (wave-uniform branches): does it derive the divisor planes, does its tile touch a border row
+    const bool interior = (a * RBP_OWN_ROWS - 8 >= 1) && (a * RBP_OWN_ROWS - 8 + 255 <= nrows - 2);
+#define RBP_MARCH(F0_, NF_, D_, I_)                                                                                                 \
+    rbp_sweep_wave<Mdl, S, F0_, NF_, D_, I_>(P, dout0, dout1, Kring, Qring, Oring, Hring, s, lane, r, nrows, ncols, j0, j1, xbase, nsteps, omega, col0, fo, mirror)
+#define RBP_ROLES(F0_, NF_)                                                                                                         \
+    do {                                                                                                                            \
+        if (FIRST && s == 0) {                                                                                                      \
+            if (interior) RBP_MARCH(F0_, NF_, true, true);                                                                          \
+            else RBP_MARCH(F0_, NF_, true, false);                                                                                  \
+        } else {                                                                                                                    \
+            if (interior) RBP_MARCH(F0_, NF_, false, true);                                                                         \
+            else RBP_MARCH(F0_, NF_, false, false);                                                                                 \
+        }                                                                                                                           \
+    } while (0)
     if constexpr (NW == 2) {
         // wave 0..7 -> (sweep, field): (1,0) (0,0) (0,1) (1,1) (3,0) (2,0) (2,1) (3,1); SIMD classes {0,4,L} {1,5} {2,6} {3,7}
         const int q = wave & 3;
         const int s = (RBP_ROLE_REMAP && S == 4) ? ((wave >> 2) << 1) | ((q == 0 || q == 3) ? 1 : 0) : wave >> 1;
         const int fld = (RBP_ROLE_REMAP && S == 4) ? (wave >> 1) & 1 : wave & 1;
-        if (fld == 0) rbp_sweep_wave<Mdl, S, FIRST, 0, 1>(P, dout0, dout1, Kring, Qring, Oring, Hring, s, lane, r, nrows, ncols, j0, j1, xbase, nsteps, omega, col0, fo, mirror);
-        else rbp_sweep_wave<Mdl, S, FIRST, 1, 1>(P, dout0, dout1, Kring, Qring, Oring, Hring, s, lane, r, nrows, ncols, j0, j1, xbase, nsteps, omega, col0, fo, mirror);
+        if (fld == 0) RBP_ROLES(0, 1);
+        else RBP_ROLES(1, 1);
     } else {
         const int s = (RBP_ROLE_REMAP && wave < 2) ? wave ^ 1 : wave; // the loader (wave S) shares a SIMD with wave 0: sweep 1, not sweep 0
-        rbp_sweep_wave<Mdl, S, FIRST, 0, NIT>(P, dout0, dout1, Kring, Qring, Oring, Hring, s, lane, r, nrows, ncols, j0, j1, xbase, nsteps, omega, col0, fo, mirror);
+        RBP_ROLES(0, NIT);
     }
+#undef RBP_ROLES
+#undef RBP_MARCH
 }
 
 } // namespace pdeip
