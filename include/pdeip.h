@@ -114,6 +114,27 @@ int pdeip_debug_raise_abort(void);
  * PDEIP_PERSIST_XCD=1), built on the device as a call builds it and copied to `table` (16 + B*T ints: list offsets 0..8, items
  * b | t << 16 from int 16 on). */
 int pdeip_debug_persist_order(int B, int T, int affine, int *table);
+/* Diagnostic: what a point-SOR *_dev call of this shape would launch, decided as the call decides it (csrc/pdeip_sor_plan.hpp) and
+ * under the PDEIP_* knobs of the environment, without launching anything.
+ *   model       PDEIP_PLAN_*; aligned16: every plane of the caller's is 16-byte aligned; has_dst: a *_dev_to call whose destination
+ *               is not the iterate (ignored for the 9-point model, which has none)
+ *   num_cus, rb2_slots, rbp_slots   compute units, resident waves of the two-sweep march, resident workgroups of k_sor_rbp.  A
+ *               value of 0 is asked from the current device as a call asks it; with all three positive the entry makes no HIP
+ *               call and works on a machine without a GPU.
+ *   info        PDEIP_PLAN_INFO ints: family (0 nothing to relax, 1 exact order, 2 k_sor_small, 3 k_sor_rb, 4 k_sor_rbp with its 2 / 1
+ *               tail, 5 the 9-point four-colour chain), exact-order form (1 persistent, 2 walker, 3 one launch per front), whether a
+ *               closing device-to-device copy follows, whether the iterate is copied to the destination first, whether
+ *               k_persist_setup runs (these three are not counted by pdeip_last_launch_count()), A, B, NC, W, last_m of the
+ *               exact-order forms, and the number of launch records.
+ *   records     the launches pdeip_last_launch_count() counts, in order (the first `capacity` of them; may be NULL with capacity 0),
+ *               PDEIP_PLAN_RECORD ints each: kind (1 k_sor_rbp, 2 / 3 k_sor_rb two- / one-sweep, 4 k_sor_small, 5 / 6 k_pde8_colour2 /
+ *               k_pde8_colour, 7 pack, 8 persistent walk, 9 walker, 10 derive, 11 a front, 12 border fill), sweeps, first launch of a
+ *               red-black call, strip width, row tiles, units, grid x, buffer read and buffer written (0 the caller's iterate, 1 the
+ *               scratch copy, 2 the destination).  pdeip_disp_sor_llin_sym4_dev runs its plan twice; so do the records. */
+enum { PDEIP_PLAN_ELIN4 = 0, PDEIP_PLAN_LLIN4, PDEIP_PLAN_DISP4, PDEIP_PLAN_PDE4, PDEIP_PLAN_PDE8, PDEIP_PLAN_DISPSYM4 };
+enum { PDEIP_PLAN_INFO = 11, PDEIP_PLAN_RECORD = 9 };
+int pdeip_debug_plan_sor(int model, int nrows, int ncols, int nframes, int iter, int mode, int aligned16, int has_dst, int num_cus,
+                         int rb2_slots, int rbp_slots, int *info, int *records, int capacity);
 /* Diagnostic: compares the fused pipeline's fast reciprocal (v_rcp_f32 + one Newton step, taken by the divisor planes of
  * opticalflowSolvers.c:111-127 when every denominator is a normal number with a normal reciprocal) with the IEEE quotient
  * 1.0f / d for EVERY such float (exponent field 1..252, both signs); counts[0] = inputs compared, counts[1] = results that differ

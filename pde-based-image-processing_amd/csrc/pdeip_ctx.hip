@@ -48,7 +48,7 @@ void SweepTimer::stop(int launches)
 static void latch_abort(DeviceState *d)
 {
     if (!d->ws[WS_CTL] || !d->persist_used) return;
-    unsigned word = 0; // word 0 of the control block is the abort word (run_sweeps never clears it)
+    unsigned word = 0; // word 0 of the control block is the abort word (no call clears it: k_persist_setup starts at word 1)
     if (hipDeviceSynchronize() == hipSuccess && hipMemcpy(&word, d->ws[WS_CTL], sizeof word, hipMemcpyDeviceToHost) == hipSuccess && word != 0)
         d->abort_latched = true;
 }
@@ -121,16 +121,26 @@ int ensure_lds(const void *kernel, size_t bytes)
     return PDEIP_OK;
 }
 
-int resident_waves(const void *kernel, int block_threads, int waves_per_block)
+int device_cus()
+{
+    DeviceState *d = cur_dev();
+    if (d->num_cus == 0) {
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, d->device) == hipSuccess && prop.multiProcessorCount > 0) d->num_cus = prop.multiProcessorCount;
+    }
+    return d->num_cus;
+}
+
+int resident_waves(const void *kernel, int block_threads, int waves_per_block, size_t lds_bytes)
 {
     DeviceState *d = cur_dev();
     auto it = d->resident_waves.find(kernel);
     if (it != d->resident_waves.end()) return it->second;
-    int blocks = 0, dev = 0;
-    hipDeviceProp_t prop;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, kernel, block_threads, 0) != hipSuccess) blocks = 1;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) prop.multiProcessorCount = 256;
-    const int slots = (blocks > 0 ? blocks : 1) * waves_per_block * prop.multiProcessorCount;
+    int blocks = 0;
+    if (lds_bytes > 0) (void)ensure_lds(kernel, lds_bytes); // ask about the launch as it will be made (a refusal is reported by the launch's own opt-in)
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, kernel, block_threads, lds_bytes) != hipSuccess) blocks = 1;
+    const int cus = device_cus();
+    const int slots = (blocks > 0 ? blocks : 1) * waves_per_block * (cus > 0 ? cus : 256);
     d->resident_waves[kernel] = slots;
     return slots;
 }
@@ -171,19 +181,6 @@ int check_deriv_dims(const char *who, int nrows, int ncols, int nframes)
     if (nrows < 4 || ncols < 4) return set_err(PDEIP_ERR_ARG, "%s: the 5-tap filters need at least 4x4 pixels (got %dx%d)", who, nrows, ncols);
     return PDEIP_OK;
 }
-
-// Columns per red-black unit.  Narrow strips mean more waves in flight but more halo re-reads
-// ((TJ+2)/TJ coefficient, (TJ+4)/TJ iterate columns).  12 is the measured optimum at 4K (2880 units)
-// and at 1080p (10-12 equal, 6-8 slower); a strip stride that is a multiple of a large power of two
-// aliases on HBM channels (TJ=16 at nrows=2160 is 15 % slower than 12).  PDEIP_RB_TJ overrides.
-int pick_rb_tj(int nrows, int ncols)
-{
-    (void)nrows;
-    (void)ncols;
-    const int forced = g.rb_tj > 0 ? g.rb_tj : env_int("PDEIP_RB_TJ", 0);
-    return forced > 0 ? (forced < 2 ? 2 : forced) : 12;
-}
-
 
 // Environment knobs of an unchanged MATLAB session: read once, before the first call
 // that needs them; explicit pdeip_set_mode / pdeip_set_device(s) calls made earlier win.

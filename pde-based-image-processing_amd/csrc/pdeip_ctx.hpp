@@ -93,7 +93,7 @@ int set_err(int code, const char *fmt, ...);
     } while (0)
 
 // Times a run of sweep launches when profiling is on (pdeip_profile_*): from the first launch's begin to the last launch's end.
-// Two forms.  Where the number of launches is known before the first one (the red-black chain of run_sweeps) the two events are
+// Two forms.  Where the number of launches is known before the first one (run_chain of pdeip_sor5.hip) the two events are
 // handed to the launches themselves: launch_timed() binds start_for(i) / stop_for(i) -- null for all but the first and the last
 // launch -- to the kernel's own dispatch packet, so the timed stream carries the same packets as the untimed one.  Everywhere
 // else (exact order, k_sor_small, line relaxation, the persistent kernels) the constructor and stop() record the events as
@@ -122,8 +122,11 @@ DeviceState *cur_dev();
 int ws_get(int slot, size_t bytes, float **out);
 // Opt a kernel into `bytes` of dynamic LDS on the current device (needed above 64 KiB), once per device and size.
 int ensure_lds(const void *kernel, size_t bytes);
-// Waves of `kernel` the current device holds at once (blocks per CU x waves per block x CUs), cached per device.
-int resident_waves(const void *kernel, int block_threads, int waves_per_block);
+// Compute units of the current device, cached per device; 0: the query failed (every caller has its own fallback).
+int device_cus();
+// Waves of `kernel` the current device holds at once (blocks per CU x waves per block x CUs) when a workgroup takes `lds_bytes` of
+// dynamic LDS, cached per device: the one place that asks the runtime about occupancy.
+int resident_waves(const void *kernel, int block_threads, int waves_per_block, size_t lds_bytes = 0);
 
 int check_dims(const char *who, int nrows, int ncols, int nframes);
 int check_mode(const char *who, int mode);
@@ -131,7 +134,6 @@ int check_solver(const char *who, int solver);
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 int env_int(const char *name, int dflt);
 int check_deriv_dims(const char *who, int nrows, int ncols, int nframes);
-int pick_rb_tj(int nrows, int ncols); // columns per unit of the one-sweep red-black kernels
 // Device-to-device copy of n floats on stream s by a kernel of the library's own (16 bytes per lane, grid-stride): the runtime's
 // blit kernel behind hipMemcpyAsync moves a 33 MB plane in 81 us (0.8 TB/s); this one in ~13.  Capturable like any launch.
 int copy_d2d(hipStream_t s, float *dst, const float *src, size_t n);

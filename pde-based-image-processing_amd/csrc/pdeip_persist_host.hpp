@@ -79,15 +79,11 @@ inline int persist_prepare(hipStream_t s, int B, int iter, int nframes, size_t m
     float *ctl_f = nullptr, *order_f = nullptr;
     RC(ws_get(WS_CTL, ctl_bytes + mail_bytes, &ctl_f));
     RC(ws_get(WS_ORDER, (PERSIST_TABLE_HDR + (size_t)B * iter) * sizeof(int), &order_f));
-    DeviceState *dst = cur_dev();
-    if (dst->num_cus == 0) {
-        hipDeviceProp_t prop;
-        dst->num_cus = (hipGetDeviceProperties(&prop, dst->device) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 1;
-    }
+    const int cus = device_cus();
     // Default: the single key-ordered list -- a running workgroup only ever waits for smaller tickets, which are running or
     // finished, whatever else holds compute units.  The XCD-affine lists (3-5 % faster at 4K) are live only while every
     // workgroup of the grid is resident, which a library inside somebody else's process cannot know: opt-in, PDEIP_PERSIST_XCD=1.
-    const int affine = (env_int("PDEIP_PERSIST_XCD", 0) != 0 && nprog <= (size_t)dst->num_cus) ? 1 : 0;
+    const int affine = (env_int("PDEIP_PERSIST_XCD", 0) != 0 && nprog <= (size_t)(cus > 0 ? cus : 1)) ? 1 : 0;
     {
         // The table is built by every call, on the call's stream, by a plain launch (capturable into a HIP graph): whatever ran on the
         // device since the host last looked -- a replayed graph rewrites this buffer -- the walker launched next finds its own table.
@@ -104,7 +100,7 @@ inline int persist_prepare(hipStream_t s, int B, int iter, int nframes, size_t m
     ctl->progress = ctl->abort_flag + PERSIST_HDR_WORDS;
     ctl->order = reinterpret_cast<const int *>(order_f);
     ctl->mail = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(ctl_f) + ctl_bytes);
-    dst->persist_used = true;
+    cur_dev()->persist_used = true;
     return PDEIP_OK;
 }
 

@@ -12,81 +12,194 @@
 #include "pdeip_sor_rb.hpp"
 #include "pdeip_sor_rbp.hpp"
 #include "pdeip_sor_small.hpp"
+#include "pdeip_sor_plan.hpp"
 
 using namespace pdeip;
 
 namespace {
 
-// Strip width of the two-sweeps-per-launch kernel.  That kernel holds four column stages in registers
-// (one wave per SIMD) and is bound by its instruction stream, not by HBM: a launch takes
-// ceil(units / resident waves) rounds of (TJ + 6) steps, so the best TJ is the one that fills the last
-// round (4K: 12 -> 3 rounds of 18 steps, 133 us; 34 -> 1 round of 40 steps, 113 us; 33 -> 2 rounds, 182 us).
-template <class Mdl>
-int pick_rb2_tj(int nrows, int ncols, int nframes, int ntiles_r)
+constexpr int PS = RBP_SWEEPS;
+
+template <class Mdl> SorTraits sor_traits()
 {
-    (void)nrows;
-    const int forced = g.rb_tj > 0 ? g.rb_tj : env_int("PDEIP_RB_TJ", 0);
-    if (forced > 0) return forced < 2 ? 2 : forced;
-    // waves of this kernel the device holds at once
-    const int slots = resident_waves(reinterpret_cast<const void *>(&k_sor_rb<Mdl, true, false, true>), 64 * RB_WAVES_PER_BLOCK, RB_WAVES_PER_BLOCK);
-    int best = 12;
-    long best_cost = -1;
-    for (int tj = 2; tj <= 64; tj++) {
-        const long units = (long)ntiles_r * ((ncols + tj - 1) / tj) * nframes;
-        const long cost = ((units + slots - 1) / slots) * (tj + 6);
-        if (best_cost < 0 || cost <= best_cost) { // ties: the wider strip re-reads fewer halo columns
-            best_cost = cost;
-            best = tj;
-        }
-    }
-    return best;
+    using PL = RbpLayout<Mdl, PS>;
+    return SorTraits{Mdl::NIT, Mdl::NCF, false, 1, RB_OWN_ROWS, PL::FITS, PL::NW, RBP_OWN_ROWS, PL::nsteps(0), &SmallLayout<Mdl>::plan, &walk_width<Mdl>};
 }
 
-// Strip width of the pipelined kernel (pdeip_sor_rbp.hpp): one workgroup per CU, a launch takes
-// ceil(units / resident workgroups) rounds of nsteps(TJ) = TJ + 5S - 1 steps.
-template <class Mdl, int S>
-int pick_rbp_tj(int ncols, int nframes, int ntiles_r, const void *kernel)
+// The kernels of the red-black chain by (vector accesses, first launch of the call, two sweeps).
+template <class Mdl> auto rb_kernel(bool vec, bool first, bool two)
 {
-    using L = RbpLayout<Mdl, S>;
-    const int forced = env_int("PDEIP_RBP_TJ", 0);
-    if (forced > 0) return forced < 2 ? 2 : forced;
-    DeviceState *d = cur_dev();
-    int slots;
-    auto it = d->resident_waves.find(kernel);
-    if (it != d->resident_waves.end()) slots = it->second;
-    else {
-        int blocks = 0, dev = 0;
-        hipDeviceProp_t prop;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, kernel, L::THREADS, L::LDS_BYTES) != hipSuccess) blocks = 1;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) prop.multiProcessorCount = 256;
-        slots = (blocks > 0 ? blocks : 1) * prop.multiProcessorCount;
-        d->resident_waves[kernel] = slots;
-    }
-    int best = 64;
-    long best_cost = -1;
-    for (int tj = 8; tj <= 1024; tj++) {
-        const long units = (long)ntiles_r * ((ncols + tj - 1) / tj) * nframes;
-        const long cost = ((units + slots - 1) / slots) * L::nsteps(tj);
-        if (best_cost < 0 || cost < best_cost) {
-            best_cost = cost;
-            best = tj;
-        }
-    }
-    return best;
+    static constexpr decltype(&k_sor_rb<Mdl, true, true, true>) table[2][2][2] = {
+        {{&k_sor_rb<Mdl, false, false, false>, &k_sor_rb<Mdl, false, false, true>}, {&k_sor_rb<Mdl, false, true, false>, &k_sor_rb<Mdl, false, true, true>}},
+        {{&k_sor_rb<Mdl, true, false, false>, &k_sor_rb<Mdl, true, false, true>}, {&k_sor_rb<Mdl, true, true, false>, &k_sor_rb<Mdl, true, true, true>}}};
+    return table[vec][first][two];
 }
+template <class Mdl> auto rbp_kernel(bool first) { return first ? &k_sor_rbp<Mdl, PS, true> : &k_sor_rbp<Mdl, PS, false>; }
+
+// A device fact the planner was not given, asked from the current device (cached per device).  Both instantiations of k_sor_rbp
+// take the same LDS, more than half of a compute unit's: one workgroup per compute unit either way, so one of them is asked.
+template <class Mdl> int device_fact(int fact)
+{
+    using PL = RbpLayout<Mdl, PS>;
+    if (fact == FACT_CUS) return device_cus() > 0 ? device_cus() : 1;
+    if (fact == FACT_RB2) return resident_waves(reinterpret_cast<const void *>(rb_kernel<Mdl>(true, false, true)), 64 * RB_WAVES_PER_BLOCK, RB_WAVES_PER_BLOCK);
+    return resident_waves(reinterpret_cast<const void *>(rbp_kernel<Mdl>(true)), PL::THREADS, 1, PL::LDS_BYTES);
+}
+
+template <class Mdl> SorPlan plan_for(const SorShape &sh, const SorDevice &dev) { return plan_sor(sor_traits<Mdl>(), sh, dev, &device_fact<Mdl>); }
 
 // ------------------------------------------------------------------------------------------------
 // sweep drivers (5-point models)
 // ------------------------------------------------------------------------------------------------
 
-// Runs `iter` sweeps of model Mdl on the iterate buffers P.it_out (in place from the caller's
-// point of view).  P.ro and P.cf must be set, with the RAW planes in the two derived slots
-// (Mdl::D0, Mdl::D1); the derived planes (divisors) are built into workspace here.
+// A call, as the runners see it.  P.it_out holds the caller's iterate, P.ro and P.cf are set, with the RAW planes in the two
+// derived slots (Mdl::D0, Mdl::D1); aux0 / aux1 are the workspace planes the derived ones (divisors) are built into.
+template <class Mdl> struct SweepCall {
+    hipStream_t s;
+    SweepPlanes<Mdl> P;
+    int nrows, ncols, nframes, iter;
+    float omega;
+    int col0;
+    size_t n; // pixels of a frame
+    float *aux0, *aux1;
+    float *const *dst;
+};
+
+// Exact order: the wavefront kernels relax in place, on the destination when there is one (run_sweeps copied the iterate there).
+template <class Mdl> int run_exact(const SweepCall<Mdl> &c, const SorPlan &plan)
+{
+    constexpr int NIT = Mdl::NIT;
+    SweepPlanes<Mdl> P = c.P;
+    hipStream_t s = c.s;
+    for (int f = 0; f < NIT; f++) {
+        if (c.dst) P.it_out[f] = c.dst[f];
+        P.it_in[f] = P.it_out[f];
+    }
+    if (plan.form == FORM_FRONT) {
+        hipLaunchKernelGGL(k_derive<Mdl>, pixel_grid(c.nrows, c.ncols, c.nframes), dim3(256), 0, s, P, c.aux0, c.aux1, c.nrows, c.ncols, c.n);
+        P.cf[Mdl::D0] = c.aux0;
+        P.cf[Mdl::D1] = c.aux1;
+        const dim3 grid((unsigned)(plan.B * c.iter), (unsigned)c.nframes);
+        constexpr size_t lds = ExactLayout<Mdl>::LDS_BYTES;
+        RC(ensure_lds(reinterpret_cast<const void *>(&k_sor_exact<Mdl>), lds)); // > 64 KiB of dynamic LDS needs an explicit opt-in
+        SweepTimer timer(s);
+        for (int m = 0; m <= plan.last_m; m++)
+            hipLaunchKernelGGL(k_sor_exact<Mdl>, grid, dim3(128), lds, s, P, c.nrows, c.ncols, plan.A, plan.B, c.iter, m, c.omega, c.n);
+        timer.stop(plan.last_m + 1);
+        tls.last_launches += 1 + plan.last_m + 1;
+    } else {
+        // pre-pass of the persistent forms: the derived planes AND the raw ones, packed per pixel (k_pack_coefficients)
+        float *pack = nullptr;
+        RC(ws_get(WS_PACK, c.n * c.nframes * Mdl::NCF * sizeof(float), &pack));
+        hipLaunchKernelGGL(k_pack_coefficients<Mdl>, pixel_grid(c.nrows, c.ncols, c.nframes), dim3(256), 0, s, P, pack, c.nrows, c.ncols, c.n);
+        // schedule table, control block, mailbox: one 8-byte {value, tag} word per (frame, sweep, strip, field, row)
+        PersistCtl ctl{};
+        RC(persist_prepare(s, plan.B, c.iter, c.nframes, (size_t)c.nframes * c.iter * plan.B * NIT * (size_t)plan.NC * EX_CH * sizeof(unsigned long long), &ctl));
+        SweepTimer timer(s);
+        if (plan.form == FORM_WALK) {
+            RC(walk_launch<Mdl>(s, P, pack, ctl, c.nrows, c.ncols, plan.B, c.iter, plan.NC, c.nframes, c.omega, c.n, plan.W));
+        } else { // one launch, progress counters instead of one launch per front
+            constexpr size_t plds = ExactLayout<Mdl>::LDS_BYTES + 16;
+            RC(ensure_lds(reinterpret_cast<const void *>(&k_sor_exact_persist<Mdl>), plds));
+            hipLaunchKernelGGL(k_sor_exact_persist<Mdl>, dim3((unsigned)(plan.B * c.iter * c.nframes)), dim3(exp_threads<Mdl>()), plds, s, P, pack, ctl, c.nrows,
+                               c.ncols, plan.B, c.iter, plan.NC, c.nframes, c.omega, c.n);
+        }
+        timer.stop(1);
+        tls.last_launches += 2;
+    }
+    const int nb = 2 * c.ncols + 2 * (c.nrows - 2);
+    hipLaunchKernelGGL(k_fill_borders, dim3((nb + 255) / 256, c.nframes, NIT), dim3(256), 0, s, P.it_out[0], P.it_out[NIT - 1], NIT, c.nrows, c.ncols, c.n);
+    tls.last_launches++;
+    HIPCHK(hipGetLastError());
+    return PDEIP_OK;
+}
+
+// The buffers a launch reads and writes: buf[BUF_*][field].
+template <class Mdl> void bind_buffers(SweepPlanes<Mdl> &P, float *(&buf)[3][Mdl::NIT], const SorLaunch &l)
+{
+    for (int f = 0; f < Mdl::NIT; f++) {
+        P.it_in[f] = buf[l.src][f];
+        P.it_out[f] = buf[l.dst][f];
+    }
+}
+
+// k_sor_small: later launches of the call run in place on the result.
+template <class Mdl> int run_small(const SweepCall<Mdl> &c, const SorPlan &plan, float *(&buf)[3][Mdl::NIT])
+{
+    using SL = SmallLayout<Mdl>;
+    const SmallPlan &sp = plan.small;
+    SweepPlanes<Mdl> P = c.P;
+    RC(ensure_lds(reinterpret_cast<const void *>(&k_sor_small<Mdl>), sp.lds));
+    unsigned *counter = nullptr, *abort_word = nullptr;
+    if (sp.nslabs > 1) {
+        float *p = nullptr;
+        RC(ws_get(WS_SMALL, 64, &p));
+        counter = reinterpret_cast<unsigned *>(p);
+        RC(ws_get(WS_CTL, 16, &p));
+        abort_word = reinterpret_cast<unsigned *>(p);
+    }
+    DeviceState *d = cur_dev();
+    SweepTimer timer(c.s);
+    RC(for_each_launch(plan, [&](const SorLaunch &l) {
+        bind_buffers<Mdl>(P, buf, l);
+        const bool gated = sp.nslabs > 1 && l.src == l.dst; // a cut frame relaxed in place: the load counter
+        if (gated) d->persist_used = true; // a timed-out wait raises the sticky abort word
+        hipLaunchKernelGGL(k_sor_small<Mdl>, dim3((unsigned)sp.nslabs, (unsigned)c.nframes), dim3(SL::THREADS), sp.lds, c.s, P, c.nrows, c.ncols, l.sweeps,
+                           c.omega, c.col0, c.n, sp.W, gated ? counter : nullptr, abort_word);
+        tls.last_launches++;
+        return PDEIP_OK;
+    }));
+    timer.stop(plan.nlaunch);
+    HIPCHK(hipGetLastError());
+    return PDEIP_OK;
+}
+
+#ifndef PDEIP_TIMER_MARKERS
+#define PDEIP_TIMER_MARKERS 0 /* A/B aid: record the two events as markers around the chain, as every other path does */
+#endif
+
+// The red-black chain.  In place, an odd number of launches ends in the scratch copy and costs one device-to-device copy of the
+// iterate; with a destination the chain input -> (scratch | dst) ... -> dst needs no copy at all.
+template <class Mdl> int run_chain(const SweepCall<Mdl> &c, const SorPlan &plan, float *(&buf)[3][Mdl::NIT])
+{
+    using PL = RbpLayout<Mdl, PS>;
+    SweepPlanes<Mdl> P = c.P;
+    hipStream_t s = c.s;
+    SweepTimer timer(s, PDEIP_TIMER_MARKERS ? 0 : plan.nlaunch); // the events ride on the first and the last launch: no packet of their own
+    int done = 0; // sweeps
+    RC(for_each_launch(plan, [&](const SorLaunch &l) {
+        bind_buffers<Mdl>(P, buf, l);
+        hipEvent_t const e0 = timer.start_for(l.index), e1 = timer.stop_for(l.index);
+        if (l.kind == K_RBP) {
+            RC(ensure_lds(reinterpret_cast<const void *>(rbp_kernel<Mdl>(l.first)), PL::LDS_BYTES));
+            // the derived planes leave the kernel only if a later launch of this call reads them
+            const bool keep = l.first && done + PS < c.iter;
+            launch_timed(rbp_kernel<Mdl>(l.first), dim3((unsigned)l.gridx, (unsigned)c.nframes), dim3(PL::THREADS), PL::LDS_BYTES, s, e0, e1, P, keep ? c.aux0 : nullptr,
+                         keep ? c.aux1 : nullptr, c.nrows, c.ncols, l.tj, l.tiles, l.units, c.omega, c.col0, c.n, plan.mirror_mode);
+        } else { // the first launch also builds the divisor planes
+            launch_timed(rb_kernel<Mdl>(plan.vec, l.first, l.sweeps == 2), dim3((unsigned)l.gridx, (unsigned)c.nframes), dim3(64 * RB_WAVES_PER_BLOCK), 0, s, e0, e1, P,
+                         l.first ? c.aux0 : nullptr, l.first ? c.aux1 : nullptr, c.nrows, c.ncols, l.tj, l.tiles, l.units, c.omega, c.col0, c.n);
+        }
+        if (l.first) {
+            P.cf[Mdl::D0] = c.aux0;
+            P.cf[Mdl::D1] = c.aux1;
+        }
+        done += l.sweeps;
+        tls.last_launches++;
+        return PDEIP_OK;
+    }));
+    timer.stop(plan.nlaunch);
+    if (plan.copy_back)
+        for (int f = 0; f < Mdl::NIT; f++) RC(copy_d2d(s, buf[BUF_CALLER][f], buf[BUF_SCRATCH][f], c.n * c.nframes));
+    HIPCHK(hipGetLastError());
+    return PDEIP_OK;
+}
+
+// Runs `iter` sweeps of model Mdl on the iterate buffers P.it_out (in place from the caller's point of view): plan, fetch the
+// workspace, run the plan's family.
 //
 // `dst` (optional): NIT buffers that receive the result while the caller's iterate in P.it_out is only READ -- what a
-// gateway does anyway (copy in, solve on the output: Oflow_sor_elin4_2d.c:341-346).  The red-black launches ping-pong
-// between buffers, so with a separate destination the chain input -> (scratch | dst) ... -> dst needs no copy at all; in
-// place, an odd number of launches ends in the scratch copy and costs one device-to-device copy of the iterate.
+// gateway does anyway (copy in, solve on the output: Oflow_sor_elin4_2d.c:341-346).
 template <class Mdl>
 int run_sweeps(hipStream_t s, SweepPlanes<Mdl> P, int nrows, int ncols, int nframes, int iter,
                float omega, int mode, int col0, float *const *dst = nullptr)
@@ -94,270 +207,69 @@ int run_sweeps(hipStream_t s, SweepPlanes<Mdl> P, int nrows, int ncols, int nfra
     constexpr int NIT = Mdl::NIT;
     const size_t n = (size_t)nrows * ncols;
     tls.last_launches = 0;
-    if (mode == PDEIP_MODE_LINE_SCAN) mode = PDEIP_MODE_EXACT_ORDER; // LINE_SCAN only changes line relaxation
-    if (dst != nullptr) {
-        bool same = true;
-        for (int f = 0; f < NIT; f++) same = same && dst[f] == P.it_out[f];
-        if (same) dst = nullptr;
-    }
-    if (iter <= 0) {
-        if (dst != nullptr)
-            for (int f = 0; f < NIT; f++) RC(copy_d2d(s, dst[f], P.it_out[f], n * nframes));
-        return PDEIP_OK;
-    }
-    if (dst != nullptr && mode == PDEIP_MODE_EXACT_ORDER) { // the wavefront kernels relax in place: on the destination
-        for (int f = 0; f < NIT; f++) {
-            RC(copy_d2d(s, dst[f], P.it_out[f], n * nframes));
-            P.it_out[f] = dst[f];
-        }
-        dst = nullptr;
-    }
-    float *aux0 = nullptr, *aux1 = nullptr;
-    RC(ws_get(WS_AUX0, n * nframes * sizeof(float), &aux0));
-    RC(ws_get(WS_AUX1, n * nframes * sizeof(float), &aux1));
-
-    if (mode == PDEIP_MODE_EXACT_ORDER) {
-        const float *raw_cf[Mdl::NCF];
-        for (int f = 0; f < Mdl::NCF; f++) raw_cf[f] = P.cf[f];
-        const int A = (nrows - 2 + 63 + EX_R - 1) / EX_R;
-        const int B = (ncols - 2 + 63) / 64;
-        const int last_m = (A - 1) + 2 * (B - 1) + 3 * (iter - 1);
-        for (int f = 0; f < NIT; f++) P.it_in[f] = P.it_out[f];
-        // Launch-per-front or persistent?  The persistent form wins at every iter and frame size (tools/time_exact_persist.py:
-        // 4K 2.70 vs 2.87 ms at iter=4 -- each strip has to trail its west neighbour by 64 rows plus the hand-off latency either
-        // way --, 1.4x at iter=20, 1.3x at 1080p, 2.4x at 34x60: no per-front launch, sweeps overlap more tightly).
-        // PDEIP_EXACT_PERSIST = 0 falls back to one launch per front.
-        const bool persist = env_int("PDEIP_EXACT_PERSIST", 1) != 0;
-        if (persist && B <= 0xffff && iter <= 0x7fff && n * Mdl::NCF * sizeof(float) < 0xffff0000ull && ncols <= 65535) {
-            // pre-pass of the persistent form: the derived planes AND the raw ones, packed per pixel (k_pack_coefficients)
-            float *pack = nullptr;
-            for (int f = 0; f < Mdl::NCF; f++) P.cf[f] = raw_cf[f];
-            RC(ws_get(WS_PACK, n * nframes * Mdl::NCF * sizeof(float), &pack));
-            hipLaunchKernelGGL(k_pack_coefficients<Mdl>, pixel_grid(nrows, ncols, nframes), dim3(256), 0, s, P, pack, nrows, ncols, n);
-            tls.last_launches++;
-            // ---- persistent form: one launch, progress counters instead of one launch per front ----
-            const int NC = (nrows - 2 + 63 + EX_CH - 1) / EX_CH;
-            // Round 3's walker (pdeip_sor_walk.hpp, launched from pdeip_walk5.hip: LDS-DMA loader, three chunk buffers, strips of
-            // W columns) is an opt-in, PDEIP_EXACT_WALK=1: measured against round 2's k_sor_exact_persist in the same runs it is
-            // 15 % faster at 4K with one sweep per call, 2-5 % at iter = 4, and 5-25 % SLOWER on frames below 1080p and for the
-            // single-field models (five waves and a longer prologue per walker) -- the walk is paced by what one compute unit's
-            // memory pipeline takes per chunk and by the strips' start-up chain, not by the loader's instruction count
-            // (exact order; profiles/NOTES.md).
-            const bool walk = env_int("PDEIP_EXACT_WALK", 0) != 0;
-            const int W = walk ? walk_width<Mdl>(nrows, ncols, nframes, iter) : 64;
-            const int BW = (ncols - 2 + W - 1) / W;
-            // schedule table, control block, mailbox: one 8-byte {value, tag} word per (frame, sweep, strip, field, row)
-            PersistCtl ctl{};
-            RC(persist_prepare(s, BW, iter, nframes, (size_t)nframes * iter * BW * NIT * (size_t)NC * EX_CH * sizeof(unsigned long long), &ctl));
-            SweepTimer timer(s);
-            if (walk) {
-                RC(walk_launch<Mdl>(s, P, pack, ctl, nrows, ncols, BW, iter, NC, nframes, omega, n, W));
-            } else {
-                constexpr size_t plds = ExactLayout<Mdl>::LDS_BYTES + 16;
-                RC(ensure_lds(reinterpret_cast<const void *>(&k_sor_exact_persist<Mdl>), plds));
-                hipLaunchKernelGGL(k_sor_exact_persist<Mdl>, dim3((unsigned)(BW * iter * nframes)), dim3(exp_threads<Mdl>()), plds, s, P, pack, ctl, nrows, ncols, BW, iter, NC, nframes, omega, n);
-            }
-            timer.stop(1);
-            tls.last_launches++;
-            const int nb = 2 * ncols + 2 * (nrows - 2);
-            hipLaunchKernelGGL(k_fill_borders, dim3((nb + 255) / 256, nframes, NIT), dim3(256), 0, s,
-                               P.it_out[0], P.it_out[NIT - 1], NIT, nrows, ncols, n);
-            tls.last_launches++;
-            HIPCHK(hipGetLastError());
-            return PDEIP_OK;
-        }
-        hipLaunchKernelGGL(k_derive<Mdl>, pixel_grid(nrows, ncols, nframes), dim3(256), 0, s, P, aux0, aux1, nrows, ncols, n);
-        tls.last_launches++;
-        P.cf[Mdl::D0] = aux0;
-        P.cf[Mdl::D1] = aux1;
-        const dim3 grid((unsigned)(B * iter), (unsigned)nframes);
-        constexpr size_t lds = ExactLayout<Mdl>::LDS_BYTES;
-        RC(ensure_lds(reinterpret_cast<const void *>(&k_sor_exact<Mdl>), lds)); // > 64 KiB of dynamic LDS needs an explicit opt-in
-        SweepTimer timer(s);
-        for (int m = 0; m <= last_m; m++) {
-            hipLaunchKernelGGL(k_sor_exact<Mdl>, grid, dim3(128), lds, s, P, nrows, ncols, A, B, iter, m, omega, n);
-            tls.last_launches++;
-        }
-        timer.stop(last_m + 1);
-        const int nb = 2 * ncols + 2 * (nrows - 2);
-        hipLaunchKernelGGL(k_fill_borders, dim3((nb + 255) / 256, nframes, NIT), dim3(256), 0, s,
-                           P.it_out[0], P.it_out[NIT - 1], NIT, nrows, ncols, n);
-        tls.last_launches++;
-        HIPCHK(hipGetLastError());
-        return PDEIP_OK;
-    }
-
-    // small frames: the iterate resident in LDS, one launch per (up to) four sweeps (pdeip_sor_small.hpp); PDEIP_RB_SMALL=0 disables
-    const bool small_enabled = env_int("PDEIP_RB_SMALL", 1) != 0; // read per call: the tests switch it
-    if (small_enabled) {
-        using SL = SmallLayout<Mdl>;
-        const int qpref = env_int("PDEIP_SMALL_Q", 1); // 1 measured fastest at every scale (tools/time_small.py): short workgroups beat little redundancy
-        SmallPlan sp = SL::plan(nrows, ncols, iter, qpref < 1 ? 1 : qpref);
-        int per_launch = iter;
-        if (!sp.ok && iter > SMALL_MAX_SWEEPS) {
-            sp = SL::plan(nrows, ncols, SMALL_MAX_SWEEPS, qpref < 1 ? 1 : qpref);
-            per_launch = SMALL_MAX_SWEEPS;
-        }
-        // a cut frame relaxed in place needs every workgroup resident at once (the load counter below): at most one workgroup
-        // per compute unit, with an eighth of the device left for whatever else is running
-        if (sp.ok && sp.nslabs > 1) {
-            DeviceState *d = cur_dev();
-            if (d->num_cus == 0) {
-                hipDeviceProp_t prop;
-                d->num_cus = (hipGetDeviceProperties(&prop, d->device) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 1;
-            }
-            if ((long)sp.nslabs * nframes > (long)d->num_cus - d->num_cus / 8) sp.ok = false;
-        }
-        if (sp.ok) {
-            RC(ensure_lds(reinterpret_cast<const void *>(&k_sor_small<Mdl>), sp.lds));
-            unsigned *counter = nullptr, *abort_word = nullptr;
-            if (sp.nslabs > 1) {
-                float *p = nullptr;
-                RC(ws_get(WS_SMALL, 64, &p));
-                counter = reinterpret_cast<unsigned *>(p);
-                RC(ws_get(WS_CTL, 16, &p));
-                abort_word = reinterpret_cast<unsigned *>(p);
-            }
-            DeviceState *d = cur_dev();
-            for (int f = 0; f < NIT; f++) {
-                P.it_in[f] = P.it_out[f];
-                if (dst) P.it_out[f] = dst[f];
-            }
-            SweepTimer timer(s);
-            int nl = 0;
-            for (int it = 0; it < iter; it += per_launch, nl++) {
-                const int k = iter - it < per_launch ? iter - it : per_launch;
-                const bool gated = sp.nslabs > 1 && P.it_in[0] == P.it_out[0];
-                if (gated) d->persist_used = true; // a timed-out wait raises the sticky abort word
-                hipLaunchKernelGGL(k_sor_small<Mdl>, dim3((unsigned)sp.nslabs, (unsigned)nframes), dim3(SL::THREADS), sp.lds, s, P, nrows, ncols, k,
-                                   omega, col0, n, sp.W, gated ? counter : nullptr, abort_word);
-                for (int f = 0; f < NIT; f++) P.it_in[f] = P.it_out[f]; // later launches of the call: in place on the result
-            }
-            timer.stop(nl);
-            tls.last_launches += nl;
-            HIPCHK(hipGetLastError());
-            return PDEIP_OK;
-        }
-    }
-
-    // red-black: ping-pong between the caller's buffers and a scratch copy
-    float *scratch = nullptr;
-    int rc = ws_get(WS_PING, (size_t)NIT * n * nframes * sizeof(float), &scratch);
-    if (rc) return rc;
-    float *bufA[NIT], *bufB[NIT], *bufD[NIT];
-    bool vec = (nrows % 4 == 0);
+    bool same = dst != nullptr, aligned = true; // dst == it_out: in place
     for (int f = 0; f < NIT; f++) {
-        bufA[f] = P.it_out[f];
-        bufB[f] = scratch + (size_t)f * n * nframes;
-        bufD[f] = dst ? dst[f] : nullptr;
-        vec = vec && aligned16(bufA[f]) && aligned16(bufB[f]) && (!dst || aligned16(bufD[f]));
+        same = same && dst[f] == P.it_out[f];
+        aligned = aligned && aligned16(P.it_out[f]) && (!dst || aligned16(dst[f]));
     }
-    for (int f = 0; f < Mdl::NCF; f++) vec = vec && aligned16(P.cf[f]);
-    vec = vec && aligned16(aux0) && aligned16(aux1);
-    for (int f = 0; f < Mdl::NRO; f++) vec = vec && aligned16(P.ro[f]);
-
-    const int ntiles_r = rb_row_tiles(nrows, RB_OWN_ROWS);
-    const dim3 block(64 * RB_WAVES_PER_BLOCK);
-    // Two sweeps per launch where the model allows it (pdeip_sor_rb.hpp, rb_march2): same results, about
-    // two thirds of the traffic per sweep.  PDEIP_RB_FUSE=0 keeps one sweep per launch.
-    static const bool fuse_enabled = env_int("PDEIP_RB_FUSE", 1) != 0;
-    const bool fuse = fuse_enabled;
-    const int TJ1 = pick_rb_tj(nrows, ncols), TJ2 = fuse ? pick_rb2_tj<Mdl>(nrows, ncols, nframes, ntiles_r) : TJ1;
-    // Four sweeps per launch where the rings fit in LDS (pdeip_sor_rbp.hpp): the wave pipeline.  PDEIP_RB_PIPE=0 disables it.
-    constexpr int PS = 4;
-    const bool pipe_enabled = env_int("PDEIP_RB_PIPE", 1) != 0; // read per call: the tests switch it
-    // single-field models run one wave per sweep (one wave per SIMD): the pipeline only pays on large frames there
-    const bool pipe = pipe_enabled && fuse && vec && RbpLayout<Mdl, PS>::FITS && (RbpLayout<Mdl, PS>::NW == 2 || n >= (size_t)1 << 21);
-    // launches of this call (the buffer chain below needs the count up front)
-    int total_launches = 0;
-    for (int it = 0; it < iter;) {
-        const int k = (pipe && it + PS <= iter) ? PS : ((fuse && it + 2 <= iter) ? 2 : 1);
-        it += k;
-        total_launches++;
+    if (same) dst = nullptr;
+    for (int f = 0; f < Mdl::NCF; f++) aligned = aligned && aligned16(P.cf[f]);
+    for (int f = 0; f < Mdl::NRO; f++) aligned = aligned && aligned16(P.ro[f]);
+    const SorShape sh{nrows, ncols, nframes, iter, mode, aligned, dst != nullptr, 0, 0};
+    const SorPlan plan = plan_for<Mdl>(sh, SorDevice{});
+    if (plan.copy_in)
+        for (int f = 0; f < NIT; f++) RC(copy_d2d(s, dst[f], P.it_out[f], n * nframes));
+    if (plan.family == SOR_NONE) return PDEIP_OK;
+    // workspace: the derived planes, and for the chain a scratch copy of the iterate (16-byte aligned like every allocation; a
+    // frame of the vector kernels is a multiple of four floats, so every plane in them is too)
+    SweepCall<Mdl> c{s, P, nrows, ncols, nframes, iter, omega, col0, n, nullptr, nullptr, dst};
+    RC(ws_get(WS_AUX0, n * nframes * sizeof(float), &c.aux0));
+    RC(ws_get(WS_AUX1, n * nframes * sizeof(float), &c.aux1));
+    if (plan.family == SOR_EXACT) return run_exact(c, plan);
+    float *scratch = nullptr;
+    if (plan.family != SOR_SMALL) RC(ws_get(WS_PING, (size_t)NIT * n * nframes * sizeof(float), &scratch));
+    float *buf[3][NIT];
+    for (int f = 0; f < NIT; f++) {
+        buf[BUF_CALLER][f] = P.it_out[f];
+        buf[BUF_SCRATCH][f] = scratch ? scratch + (size_t)f * n * nframes : nullptr;
+        buf[BUF_DST][f] = dst ? dst[f] : nullptr;
     }
-    // launch number `flips` (0-based) reads src(flips) and writes out(flips).  In place: caller <-> scratch.  With a
-    // destination: the caller's buffers are only read by launch 0, and the outputs alternate so that the last one is dst.
-    auto buf_out = [&](int launch, int f) -> float * {
-        if (dst) return ((total_launches - 1 - launch) & 1) ? bufB[f] : bufD[f];
-        return (launch & 1) ? bufA[f] : bufB[f];
-    };
-    auto buf_in = [&](int launch, int f) -> const float * { return launch == 0 ? bufA[f] : buf_out(launch - 1, f); };
-#ifndef PDEIP_TIMER_MARKERS
-#define PDEIP_TIMER_MARKERS 0 /* A/B aid: record the two events as markers around the chain, as every other path does */
-#endif
-    SweepTimer timer(s, PDEIP_TIMER_MARKERS ? 0 : total_launches); // the events ride on the first and the last launch: no packet of their own
-    int nlaunch = 0, flips = 0; // flips: how many times the iterate changed buffers
-    for (int it = 0; it < iter;) {
-        if (pipe && it + PS <= iter) {
-            using PL = RbpLayout<Mdl, PS>;
-            const bool first = it == 0;
-            const void *kfn = first ? reinterpret_cast<const void *>(&k_sor_rbp<Mdl, PS, true>) : reinterpret_cast<const void *>(&k_sor_rbp<Mdl, PS, false>);
-            RC(ensure_lds(kfn, PL::LDS_BYTES));
-            const int ntiles_p = (nrows + RBP_OWN_ROWS - 1) / RBP_OWN_ROWS;
-            const int TJP = pick_rbp_tj<Mdl, PS>(ncols, nframes, ntiles_p, kfn);
-            const int nunits = ntiles_p * ((ncols + TJP - 1) / TJP);
-            for (int f = 0; f < NIT; f++) {
-                P.it_in[f] = buf_in(flips, f);
-                P.it_out[f] = buf_out(flips, f);
-            }
-            // the derived planes leave the kernel only if a later launch of this call reads them
-            const bool keep = first && it + PS < iter;
-            const dim3 pgrid((unsigned)nunits, (unsigned)nframes), pblock(PL::THREADS);
-            // PDEIP_RBP_SERPENTINE = 1: alternate strips march backwards (k_sor_rbp, `mirror_mode`), 2: every strip (tests).  Same bits;
-            // neighbouring strips then meet at the halo columns they share (-6 % bytes fetched), but at 4K the launch is not
-            // faster for it (97.7 vs 94.6 us, same run) -- the wave pipeline's step, not the memory system, sets its time.  Off.
-            const int serp = env_int("PDEIP_RBP_SERPENTINE", 0);
-            const int mirror_mode = serp < 0 || serp > 2 ? 0 : serp;
-            hipEvent_t const e0 = timer.start_for(nlaunch), e1 = timer.stop_for(nlaunch);
-            if (first) launch_timed(&k_sor_rbp<Mdl, PS, true>, pgrid, pblock, PL::LDS_BYTES, s, e0, e1, P, keep ? aux0 : nullptr, keep ? aux1 : nullptr, nrows, ncols, TJP, ntiles_p, nunits, omega, col0, n, mirror_mode);
-            else launch_timed(&k_sor_rbp<Mdl, PS, false>, pgrid, pblock, PL::LDS_BYTES, s, e0, e1, P, nullptr, nullptr, nrows, ncols, TJP, ntiles_p, nunits, omega, col0, n, mirror_mode);
-            if (first) {
-                P.cf[Mdl::D0] = aux0;
-                P.cf[Mdl::D1] = aux1;
-            }
-            it += PS;
-            flips++;
-            nlaunch++;
-            tls.last_launches++;
-            continue;
-        }
-        const bool two = fuse && it + 2 <= iter;
-        const int TJ = two ? TJ2 : TJ1;
-        const int nunits = ntiles_r * ((ncols + TJ - 1) / TJ);
-        const dim3 grid((unsigned)((nunits + RB_WAVES_PER_BLOCK - 1) / RB_WAVES_PER_BLOCK), (unsigned)nframes);
-        for (int f = 0; f < NIT; f++) {
-            P.it_in[f] = buf_in(flips, f);
-            P.it_out[f] = buf_out(flips, f);
-        }
-        const bool first = it == 0; // sweep 0 also builds the divisor planes
-        float *d0 = first ? aux0 : nullptr, *d1 = first ? aux1 : nullptr;
-#define PDEIP_RB_LAUNCH(V, F, T) launch_timed(&k_sor_rb<Mdl, V, F, T>, grid, block, 0, s, timer.start_for(nlaunch), timer.stop_for(nlaunch), P, d0, d1, nrows, ncols, TJ, ntiles_r, nunits, omega, col0, n)
-        if (two) {
-            if (vec) { if (first) PDEIP_RB_LAUNCH(true, true, true); else PDEIP_RB_LAUNCH(true, false, true); }
-            else     { if (first) PDEIP_RB_LAUNCH(false, true, true); else PDEIP_RB_LAUNCH(false, false, true); }
-        } else {
-            if (vec) { if (first) PDEIP_RB_LAUNCH(true, true, false); else PDEIP_RB_LAUNCH(true, false, false); }
-            else     { if (first) PDEIP_RB_LAUNCH(false, true, false); else PDEIP_RB_LAUNCH(false, false, false); }
-        }
-#undef PDEIP_RB_LAUNCH
-        if (first) {
-            P.cf[Mdl::D0] = aux0;
-            P.cf[Mdl::D1] = aux1;
-        }
-        it += two ? 2 : 1;
-        flips++;
-        nlaunch++;
-        tls.last_launches++;
-    }
-    timer.stop(nlaunch);
-    if (!dst && (flips & 1)) // in place and the last launch wrote the scratch copy
-        for (int f = 0; f < NIT; f++)
-            RC(copy_d2d(s, bufA[f], bufB[f], n * nframes));
-    HIPCHK(hipGetLastError());
-    return PDEIP_OK;
+    return plan.family == SOR_SMALL ? run_small(c, plan, buf) : run_chain(c, plan, buf);
 }
 
 } // namespace
+
+extern "C" int pdeip_debug_plan_sor(int model, int nrows, int ncols, int nframes, int iter, int mode, int aligned16, int has_dst, int num_cus,
+                                    int rb2_slots, int rbp_slots, int *info, int *records, int capacity)
+{
+    const char *who = "pdeip_debug_plan_sor";
+    RC(check_dims(who, nrows, ncols, nframes));
+    RC(check_mode(who, mode));
+    if (info == nullptr || (records == nullptr && capacity > 0)) return set_err(PDEIP_ERR_ARG, "%s: null pointer", who);
+    const SorShape sh{nrows, ncols, nframes, iter, mode, aligned16 != 0, has_dst != 0, 0, 0};
+    const SorDevice dev{num_cus, rb2_slots, rbp_slots};
+    SorPlan p;
+    switch (model) {
+    case PDEIP_PLAN_ELIN4: p = plan_for<ModelElin4>(sh, dev); break;
+    case PDEIP_PLAN_LLIN4: p = plan_for<ModelLlin4>(sh, dev); break;
+    case PDEIP_PLAN_DISP4: p = plan_for<ModelDisp4>(sh, dev); break;
+    case PDEIP_PLAN_PDE4: p = plan_for<ModelPde4>(sh, dev); break;
+    case PDEIP_PLAN_PDE8: p = plan_sor_pde8(sh, dev); break;
+    case PDEIP_PLAN_DISPSYM4: p = plan_for<ModelDispSym4>(sh, dev); break;
+    default: return set_err(PDEIP_ERR_ARG, "%s: unknown model %d", who, model);
+    }
+    const int head[PDEIP_PLAN_INFO] = {p.family, p.form, p.copy_back, p.copy_in, p.persist_setup, p.A, p.B, p.NC, p.W, p.last_m, 0};
+    memcpy(info, head, sizeof head);
+    // pdeip_disp_sor_llin_sym4_dev relaxes its two fields one after the other: the plan, twice
+    for (int run = 0; run < (model == PDEIP_PLAN_DISPSYM4 ? 2 : 1); run++)
+        (void)for_each_launch(p, [&](const SorLaunch &l) {
+            const int rec[PDEIP_PLAN_RECORD] = {l.kind, l.sweeps, l.first, l.tj, l.tiles, l.units, l.gridx, l.src, l.dst};
+            if (info[10] < capacity) memcpy(records + (size_t)PDEIP_PLAN_RECORD * info[10], rec, sizeof rec);
+            info[10]++;
+            return PDEIP_OK;
+        });
+    return PDEIP_OK;
+}
 
 extern "C" int pdeip_debug_persist_order(int B, int T, int affine, int *table)
 {

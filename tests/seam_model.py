@@ -5,10 +5,12 @@ parity test happens to use decide where the strip seams, the ragged last strip a
 one card.  The cases here FORCE the geometry through the library's per-call knobs (PDEIP_RBP_TJ, PDEIP_RB_TJ,
 PDEIP_RB_SMALL, PDEIP_RB_PIPE, PDEIP_RBP_SERPENTINE, PDEIP_ALR_SMALL, PDEIP_ALR_PAIR) and carve planes at a 4-byte
 offset, so the same seams are relaxed on every card.  This module needs no GPU: it restates the launch logic of
-csrc/pdeip_sor5.hip, pdeip_sor9.hip, pdeip_line.hip and the layouts of pdeip_sor_rbp.hpp / pdeip_sor_small.hpp (it does not
+csrc/pdeip_sor_plan.hpp, pdeip_sor5.hip, pdeip_sor9.hip, pdeip_line.hip and the layouts of pdeip_sor_rbp.hpp / pdeip_sor_small.hpp (it does not
 import them: a model read off the library would agree with whatever the library does) and predicts for every case the kernel
 family, the kernels its launch chain really runs, their strip / tile geometry and the number of launches.
 tests/test_seam_matrix.py asserts that the lists cover each coverage set; tests/test_gpu_seams.py runs them.
+tests/test_sor_plan.py compares the model with the library's own plan (pdeip_debug_plan_sor, csrc/pdeip_sor_plan.hpp) on the CPU,
+over the case lists and a grid of shapes; the model stays independent: it still imports nothing from the library.
 """
 from collections import namedtuple
 
@@ -106,7 +108,7 @@ def small_launches(model, nrows, ncols, nframes, it, num_cus=256):
 # ---- run_sweeps / pdeip_pde_sor8_dev: which family, how many launches ---------------------------------------------------
 def family_of(model, nrows, ncols, nframes=1, it=4, small=True, pipe=True, aligned=True, num_cus=256):
     """The kernel family a red-black point-SOR call runs: 'small', 'rbp' (its 2/1 tail runs k_sor_rb), 'rb' or 'pde8'.
-    A call of fewer than four sweeps never launches the pipeline (run_sweeps: `pipe && it + PS <= iter`) and does not read
+    A call of fewer than four sweeps never launches the pipeline (plan_chain: `n4 = pipe ? iter / 4 : 0`) and does not read
     PDEIP_RBP_TJ: it is an 'rb' call whatever the knobs allow."""
     if model == "pde8":
         return "pde8"

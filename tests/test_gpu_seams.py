@@ -9,41 +9,16 @@ case that silently falls to another family fails on its launch count, whatever b
 sweeps runs k_sor_rb whatever the knobs allow, and is labelled so.  The knobs are read by the library per call; every one is
 restored afterwards.
 """
-import contextlib
 import functools
 import importlib
-import os
 
 import pytest
 
 import problems as pb
 import seam_model as sm
+from sor_plan import knobs, plan_sor, point_case_knobs
 
 pytestmark = pytest.mark.gpu
-
-KNOBS = ("PDEIP_RB_SMALL", "PDEIP_RB_PIPE", "PDEIP_RBP_TJ", "PDEIP_RB_TJ", "PDEIP_RBP_SERPENTINE", "PDEIP_ALR_SMALL", "PDEIP_ALR_PAIR",
-         "PDEIP_EXACT_PERSIST", "PDEIP_EXACT_WALK", "PDEIP_PDE8_PERSIST")  # the last three: the exact-order forms (test_gpu_range.py)
-
-
-@contextlib.contextmanager
-def knobs(**kv):
-    """Set the given knobs (None: unset), clear the others, and put everything back."""
-    old = {k: os.environ.get(k) for k in KNOBS}
-    try:
-        for k in KNOBS:
-            v = kv.get(k)
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = str(v)
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
 
 # planes of each model in the order of its entry point: iterate fields, read-only fields, coefficient planes
 W4, W8 = ("wW", "wN", "wE", "wS"), ("wW", "wNW", "wN", "wNE", "wE", "wSE", "wS", "wSW")
@@ -102,8 +77,7 @@ def run_point_case(pdeip, oracle, c, problem=None, omega=None):
     omega = OMEGA[c.model] if omega is None else omega
     want = want_of(oracle, c.model, p, c.it, c.col0, omega)
     d = {k: dev.to_device(v) for k, v in p.items()}
-    env = dict(PDEIP_RB_SMALL=1 if c.small else 0, PDEIP_RB_PIPE=0 if c.group == "C" else 1, PDEIP_RBP_SERPENTINE=c.serp,
-               PDEIP_RBP_TJ=c.tj if c.family == "rbp" else None, PDEIP_RB_TJ=c.tj if c.group == "C" else None)
+    env = point_case_knobs(c)
     st = torch.cuda.current_stream().cuda_stream
     tail = (c.nrows, c.ncols) + ((c.nframes,) if c.model in ("pde4", "pde8") else ()) + (c.it, omega)
     if c.model == "dispsym4":
@@ -222,3 +196,47 @@ def test_zebra_kernels_on_small_and_degenerate_frames(pdeip, oracle, model):
         assert launches == expect, "%s: %d launches, run_alr makes %d" % (sm.case_id(c), launches, expect)
         seen.add((c.small, launches == 1))
     assert seen == {(False, False), (True, True), (True, False)}  # forced off; the small side of the switch; the other side
+
+
+# The smallest shapes at which each path of the launch plan can still go wrong, with the launches each call makes and whether a
+# closing copy follows (worked out by hand: in place, an odd chain ends in the scratch copy).  Group "C" sets PDEIP_RB_PIPE=0 and
+# PDEIP_RB_TJ as for the cases of seam_model; "P" (plan) leaves the pipeline on.
+#              group family   model       rows cols frames tj   it inplace col0 serp role  small
+PLAN_CASES = [
+    (sm.Case("P", "rbp",   "elin4",    4,   9,   1,     8,   4, True,   0,   0,   None, False), 1, True),   # pipeline, two strips, the last of one column
+    (sm.Case("P", "rbp",   "llin4",    8,   18,  1,     8,   9, False,  0,   0,   None, False), 3, False),  # 4 + 4 + 1 into a destination
+    (sm.Case("C", "rb",    "llin4",    5,   40,  1,     2,   3, True,   0,   0,   None, False), 2, False),  # not vector, 2 + 1, in place
+    (sm.Case("P", "small", "elin4",    8,   8,   1,     None, 5, True,  0,   0,   None, True),  1, False),  # k_sor_small: one launch
+    (sm.Case("P", "rb",    "dispsym4", 8,   9,   1,     None, 2, True,  0,   0,   None, False), 2, True),   # one launch per field: the count doubles
+    (sm.Case("C", "pde8",  "pde8",     8,   9,   2,     None, 3, True,  0,   0,   None, False), 2, False),
+]
+
+
+@pytest.mark.parametrize("c,launches,closing_copy", PLAN_CASES, ids=[sm.case_id(c[0]) for c in PLAN_CASES])
+def test_plan_lists_the_launches_of_a_red_black_call(pdeip, oracle, c, launches, closing_copy):
+    """pdeip_debug_plan_sor, asking the device for its facts as the call does and under the call's knobs, lists as many launches as
+    the call made; the call's bits are the oracle's colour order."""
+    run_point_case(pdeip, oracle, c)
+    assert pdeip.capi.load().pdeip_last_launch_count() == launches
+    with knobs(**point_case_knobs(c)):
+        p = plan_sor(pdeip.capi, c.model, c.nrows, c.ncols, c.nframes, c.it, has_dst=not c.inplace, cus=0, rb2_slots=0, rbp_slots=0)
+    assert (p.family, len(p.launches), p.closing_copy) == (c.family, launches, closing_copy)
+
+
+@pytest.mark.parametrize("persist", [None, 0])
+def test_plan_lists_the_launches_of_an_exact_order_call(pdeip, oracle, persist):
+    """elin4, 5 x 7, two sweeps in the reference's order: the persistent form by default, one launch per front under
+    PDEIP_EXACT_PERSIST=0; the oracle's bits either way."""
+    import numpy as np
+
+    p = pb.elin4(851, 5, 7, nan_frac=0.02)
+    pdeip.mex_api.set_mode(0)
+    with knobs(PDEIP_EXACT_PERSIST=persist):
+        got = pdeip.mex_api.Oflow_sor_elin4_2d(*p.values(), np.float32(2), np.float32(1.9), np.float32(1))
+        launches = pdeip.capi.load().pdeip_last_launch_count()
+        plan = plan_sor(pdeip.capi, "elin4", 5, 7, 1, 2, mode=0, cus=0, rb2_slots=0, rbp_slots=0)
+    assert pdeip.capi.load().pdeip_persist_error() == 0, pdeip.capi.last_error()
+    for g, w in zip(got, oracle.Oflow_sor_elin4_2d(*p.values(), 2, 1.9)):
+        assert pb.bit_equal(g, w), pb.describe_mismatch(g, w)
+    assert plan.form == ("persist" if persist is None else "front")
+    assert len(plan.launches) == launches == sm.exact_launches("elin4", 5, 7, 2, plan.form)
