@@ -716,6 +716,88 @@ int pdeip_surface_fit_masked_dev(void *stream, const float *PHI, const float *D,
                                  float err_thr, float min_set_size, int iter, const unsigned *sets, unsigned long long seed,
                                  float *M_out, float *dist_out, int *ndata_out);
 
+/* ---- region competition: the inner loop of the segmentation drivers (csrc/pdeip_segmentation.hip) ---------------------------
+ * What regionCompetition() does between its MEX calls (matlab/segmentation/DispSegmentation.m:497-646, DispSegmentationSparse.m:
+ * 511-666), defined here because MATLAB's evaluation of the data term cancels catastrophically.  S level-set planes PHI [nrows x
+ * ncols x S], one data plane D [nrows x ncols], column-major float32; eps = 2^-52.  One COMPETITION ITERATION `iter` (1-based):
+ *  1. sizes     size_s = #{PHI_s >= 0} (a NaN is false).  Segments with (double)size_s < srem_thr*nrows*ncols (the product formed
+ *               in double, left to right) are removed, the survivors compacted in order, ALL surface models reset to zero and
+ *               `recalc` set.  No segment left: the call returns at once with S_out = 0 and PDEIP_OK.
+ *  2. terms     when iter is odd or recalc is set, (a)-(e), then recalc is cleared:
+ *     (a) DH, gradPHI = pdeip_cv_terms(PHI, c0, c1, dh_floor).
+ *     (b) per segment in order: pdeip_surface_fit_masked_dev with M_in = the segment's current model (a zero model IS a given
+ *         model), err_thr, min_set_size = ransac_cset, 10 hypotheses, dist_out = the segment's dist plane.  The k-th fit a call
+ *         performs (0-based, every fit counted, across iterations and scales) draws from seed + 65536*k in 64-bit wrapping
+ *         arithmetic.  With nan_fill not NaN the fit and dist see D with every NaN replaced by nan_fill; D is not modified.
+ *     (c) n_s = the number of pixels with PHI_s >= 0 and, when dist_cap is finite, (double)dist < dist_cap (a NaN dist fails);
+ *         cov_s = (sum of (double)dist over them) / n_s, the sum in float64 in a fixed order that depends neither on S nor on s
+ *         (no floating-point atomics; with dist_cap = +Inf a NaN propagates); then if (cov_s < minCOV) cov_s = minCOV (a NaN
+ *         stays; n_s == 0 gives NaN).
+ *     (d) in float64, correctly rounded sqrt and division: c_s = 1/sqrt((2*pi)*cov_s), t = (double)dist/(2*cov_s), P_s =
+ *         c_s*exp(-t).
+ *     (e) WC_s by strategy; max ignores NaN as MATLAB's does (all NaN: NaN); over the empty set of S == 1 it is 0:
+ *           PDEIP_SEG_SURFACE  WC_s = max_{r != s} P_r
+ *           PDEIP_SEG_GREEDY   as SURFACE, then WC_s = 0 where no segment has PHI >= 0 and DH_s > 0.02f
+ *           PDEIP_SEG_INVERSE  WC_s = max(Q_s, max_{r != s} [PHI_r >= 0 ? P_r : 0]) with Q_s = -(c_s*expm1(-t)) (S == 1: Q_s)
+ *         DATA_s = (float) log((P_s + eps)/(WC_s + eps)).  Q_s is the one deliberate departure from the .m, which forms c_s - P_s:
+ *         equal in exact arithmetic, but quantised at c_s*2^-53 -- the size of the eps it is added to -- so that one ulp in exp
+ *         moves DATA by 0.17 where dist -> 0.  Q_s is accurate there and the same elsewhere after rounding to single.
+ *  3. step      PHI = CV_solver_2d(PHI, DATA, DH, gradPHI, tau = 1, nu), nu = (float)(gamma_coef*(nrows*ncols)^0.7) formed in
+ *               double, all live planes in one call.  On an even iteration without removal DATA, DH and gradPHI are the previous
+ *               iteration's.
+ * The drivers' two forms are parameters; a NaN member (or prm == NULL) keeps the dense driver's value:
+ *               c0  c1  dh_floor  err_thr  gamma_coef  dist_cap  nan_fill
+ *   dense        1   1   0.06      1.0      0.001       +Inf      NaN (D is used as it is)
+ *   sparse       2   4   0.04      1.2      0.005       100       1000
+ * Refused with PDEIP_ERR_ARG before any HIP call: nrows or ncols < 2, S < 1, an order other than 1 or 2, an unknown strategy, a
+ * non-finite minCOV, srem_thr, err_thr or ransac_cset, minCOV <= 0, iterations < 0.  pdeip_set_mode does not apply. */
+#define PDEIP_SEG_SURFACE 0
+#define PDEIP_SEG_GREEDY 1
+#define PDEIP_SEG_INVERSE 2
+typedef struct pdeip_seg_params {
+    double c0, c1, dh_floor, err_thr, gamma_coef, dist_cap, nan_fill;
+} pdeip_seg_params;
+/* The stages on device pointers, asynchronous on `stream`, no host read-back (graph-capturable); partials in the library's cache.
+ * sizes_out int [S]: step 1's counts.  cov_out double [S], n_out int [S] (NULL ok): step 2c (a NaN dist_cap means +Inf).
+ * pdeip_seg_data_dev: steps 2d-e from dist [S planes], PHI, DH, cov [S] (device, double); DATA_out [S planes] must not alias an
+ * input; P_out (NULL ok) receives P as float64 planes.  P_s is formed twice (once per pass over the segments) by the same
+ * operations; every plane is read once per pass. */
+int pdeip_seg_sizes_dev(void *stream, const float *PHI, int nrows, int ncols, int S, int *sizes_out);
+int pdeip_seg_variance_dev(void *stream, const float *PHI, const float *dist, int nrows, int ncols, int S, double minCOV, double dist_cap,
+                           double *cov_out, int *n_out);
+int pdeip_seg_data_dev(void *stream, const float *dist, const float *PHI, const float *DH, const double *cov, int nrows, int ncols, int S,
+                       int strategy, float *DATA_out, double *P_out);
+/* `iterations` competition iterations on one scale, resident.  PHI, D, PHI_out [nrows x ncols x S], surf_out [ncoef x S] (ncoef =
+ * 3 | 6) and cov_out (double [S], NULL ok: the last variances, zero if none was formed) are device pointers in the _dev form and
+ * host pointers in the other; S_out, kept_out (int [S]: the 0-based input index of each survivor) and fit_counter are host
+ * pointers in both.  S_out planes / columns / entries are written.  fit_counter (NULL: starts at 0, not returned) holds k of step
+ * 2b on entry and on return, so that a caller can run one count across calls.  The _dev form reads the S sizes back once per
+ * iteration (pinned memory, one stream synchronisation) to decide removal and recalc on the host: it is NOT graph-capturable, and
+ * it has returned from its last synchronisation, not from its last kernel, when it returns.  Compaction is device-to-device plane
+ * copies; workspace from the library's cache.  PHI_out must not alias PHI.  These two calls and pdeip_region_competition clear the
+ * thread's error text on entry: after one that returned PDEIP_OK, pdeip_last_error() is empty. */
+int pdeip_seg_competition_level_dev(void *stream, const float *PHI, const float *D, int nrows, int ncols, int S, int order, int strategy,
+                                    double minCOV, float ransac_cset, int iterations, double srem_thr, unsigned long long seed,
+                                    unsigned long long *fit_counter, const pdeip_seg_params *prm, int *S_out, float *PHI_out,
+                                    float *surf_out, int *kept_out, double *cov_out);
+int pdeip_seg_competition_level(const float *PHI, const float *D, int nrows, int ncols, int S, int order, int strategy, double minCOV,
+                                float ransac_cset, int iterations, double srem_thr, unsigned long long seed, unsigned long long *fit_counter,
+                                const pdeip_seg_params *prm, int *S_out, float *PHI_out, float *surf_out, int *kept_out, double *cov_out);
+/* [PHIout SParam] = regionCompetition(D, pyramid, polyorder, sigmaLim, ransac_cset, iterations, srem_thr, PHIin, competition)
+ * (DispSegmentation.m:448-654) in one call, host pointers.  The D pyramid is built here: scale k+1 = imresize(scale k, scl_factor)
+ * through pdeip_pyr_resize_dev(cubic = 1) at ceil(size*scl_factor), K the last scale with both sides >= rc_scl x the original (and
+ * >= 3, and still shrinking); the visits are [1..K, K..1], each one level call with minCOV = sigmaLim on the PHI of the visit
+ * before, resized (cubic) to the visit's size (:648-650; the .m's initial PHI pyramid of :471-473 only fixes these sizes).  The
+ * fit counter runs across the visits.  PHI_out [nrows x ncols x S_out], surf_out: the last visit's models, kept_out as above.
+ * Also refused: scl_factor outside (0, 1), rc_scl not finite or <= 0, nrows or ncols < 3. */
+int pdeip_region_competition(const float *D, const float *PHI, int nrows, int ncols, int S, int order, int strategy, double sigmaLim,
+                             float ransac_cset, int iterations, double srem_thr, double scl_factor, double rc_scl, unsigned long long seed,
+                             const pdeip_seg_params *prm, int *S_out, float *PHI_out, float *surf_out, int *kept_out);
+/* The numbered map of DispSegmentation.m:190-198: SEG = sum over 1-based s of s*[PHI_s > 0], 0 where two or more segments hold the
+ * pixel (after which the .m's SEG(SEG > segments) = segments + 1 cannot fire).  SEG_out int32 [nrows x ncols]. */
+int pdeip_seg_label_dev(void *stream, const float *PHI, int nrows, int ncols, int S, int *SEG_out);
+int pdeip_seg_label(const float *PHI, int nrows, int ncols, int S, int *SEG_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,7 @@ PDEIP_ERR_DEVICE = 4
 PDEIP_ERR_NOMEM = 5
 MODE_EXACT_ORDER = 0
 MODE_RED_BLACK = 1
+SEG_SURFACE, SEG_GREEDY, SEG_INVERSE = 0, 1, 2  # PDEIP_SEG_*: the competition strategies
 MODE_LINE_SCAN = 2  # line relaxation in the reference's line order, a line's recurrences as parallel scans
 
 _P = ctypes.c_void_p  # float* (host or device), passed as an address
@@ -137,6 +138,18 @@ SIGNATURES = {
     "pdeip_surface_equation": [_P, _P, _I, _I, _P, _F, _F, _I, _P, ctypes.c_ulonglong, _P, _P, _P, _P],
     "pdeip_surface_equation_dev": [_P, _P, _P, _I, _I, _P, _F, _F, _I, _P, ctypes.c_ulonglong, _P, _P, _P, _P],
     "pdeip_surface_fit_masked_dev": [_P, _P, _P, _I, _I, _I, _P, _F, _F, _I, _P, ctypes.c_ulonglong, _P, _P, _P],
+    # region competition (csrc/pdeip_segmentation.hip)
+    "pdeip_seg_sizes_dev": [_P, _P, _I, _I, _I, _P],
+    "pdeip_seg_variance_dev": [_P, _P, _P, _I, _I, _I, ctypes.c_double, ctypes.c_double, _P, _P],
+    "pdeip_seg_data_dev": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P],
+    "pdeip_seg_competition_level_dev": [_P, _P, _P, _I, _I, _I, _I, _I, ctypes.c_double, _F, _I, ctypes.c_double, ctypes.c_ulonglong, _P, _P,
+                                        _P, _P, _P, _P, _P],
+    "pdeip_seg_competition_level": [_P, _P, _I, _I, _I, _I, _I, ctypes.c_double, _F, _I, ctypes.c_double, ctypes.c_ulonglong, _P, _P, _P, _P, _P,
+                                    _P, _P],
+    "pdeip_region_competition": [_P, _P, _I, _I, _I, _I, _I, ctypes.c_double, _F, _I, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                 ctypes.c_ulonglong, _P, _P, _P, _P, _P],
+    "pdeip_seg_label_dev": [_P, _P, _I, _I, _I, _P],
+    "pdeip_seg_label": [_P, _I, _I, _I, _P],
     # library state
     "pdeip_set_mode": [_I],
     "pdeip_get_mode": [],

@@ -9,6 +9,7 @@
 // The number of data rows may live on the device (the masked form): every kernel takes it as a value and as a pointer.
 #pragma once
 #include "pdeip_ctx.hpp"
+#include "pdeip_reduce.hpp"
 
 #include <cfloat>
 
@@ -203,8 +204,7 @@ __global__ void __launch_bounds__(RS_BLOCK) k_ransac_score(const float *__restri
 #pragma unroll
         for (int j = 0; j < 2; j++) u[j] = pair_step(t[2 * j], t[2 * j + 1], b4, 16); // 4j + 2*b4 + b5
         double w = pair_step(u[0], u[1], b3, 8);                                      // 4*b3 + 2*b4 + b5
-#pragma unroll
-        for (int d = 4; d >= 1; d >>= 1) w = w + __shfl_xor(w, d, 64);
+        w = wave_sum<4>(w);
         if ((lane & 7) == 0 && g0 + mine < ng) {
             s_sum[wave][g0 + mine] = w;
             s_cnt[wave][g0 + mine] = cnt;

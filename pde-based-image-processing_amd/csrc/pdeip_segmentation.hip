@@ -1,0 +1,409 @@
+// pdeip_segmentation.hip -- libpdeip.so: region competition, the inner loop of the segmentation drivers.
+//
+//   regionCompetition() between its MEX calls   matlab/segmentation/DispSegmentation.m:497-646, DispSegmentationSparse.m:511-666
+//     sizes, variance, likelihood + competitor + data term                pdeip_seg_sizes_dev / _variance_dev / _data_dev
+//     `iterations` competition iterations on one scale, resident          pdeip_seg_competition_level(_dev)
+//     the whole regionCompetition() over its scale pyramid                pdeip_region_competition
+//   the numbered segment map (DispSegmentation.m:190-198)                 pdeip_seg_label(_dev)
+//
+// Kernels: csrc/pdeip_segmentation.hpp; the contract: include/pdeip.h.  The fit is pdeip_surface_fit_masked_dev, the terms and the
+// step pdeip_cv_terms_dev / pdeip_cv_solver_dev.  pdeip_set_mode does not apply.
+//
+// Build (build.py): hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -c, one object per translation unit.
+#include "pdeip_ctx.hpp"
+#include "pdeip_segmentation.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <limits>
+#include <utility>
+#include <vector>
+
+using namespace pdeip;
+using namespace pdeip::seg;
+
+namespace {
+
+struct SegPrm {
+    float c0, c1, dh_floor, err_thr;
+    double gamma_coef, dist_cap;
+    float nan_fill;
+};
+SegPrm seg_resolve(const pdeip_seg_params *u)
+{
+    SegPrm p{1.0f, 1.0f, 0.06f, 1.0f, 0.001, std::numeric_limits<double>::infinity(), std::numeric_limits<float>::quiet_NaN()}; // DispSegmentation.m
+    if (u) {
+        if (!std::isnan(u->c0)) p.c0 = (float)u->c0;
+        if (!std::isnan(u->c1)) p.c1 = (float)u->c1;
+        if (!std::isnan(u->dh_floor)) p.dh_floor = (float)u->dh_floor;
+        if (!std::isnan(u->err_thr)) p.err_thr = (float)u->err_thr;
+        if (!std::isnan(u->gamma_coef)) p.gamma_coef = u->gamma_coef;
+        if (!std::isnan(u->dist_cap)) p.dist_cap = u->dist_cap;
+        if (!std::isnan(u->nan_fill)) p.nan_fill = (float)u->nan_fill;
+    }
+    return p;
+}
+
+int check_planes(const char *who, int nrows, int ncols, int S)
+{
+    if (nrows < 2 || ncols < 2) return set_err(PDEIP_ERR_ARG, "%s: planes must be at least 2x2 (got %dx%d)", who, nrows, ncols);
+    if (S < 1 || S > 65535) return set_err(PDEIP_ERR_ARG, "%s: number of segments must lie in 1..65535 (got %d)", who, S);
+    if ((long long)nrows * ncols > 0x7fffffffLL / 8 || (long long)nrows * ncols * S > 0x7fffffffLL / 8)
+        return set_err(PDEIP_ERR_ARG, "%s: planes too large", who);
+    return PDEIP_OK;
+}
+
+int check_strategy(const char *who, int strategy)
+{
+    if (strategy != PDEIP_SEG_SURFACE && strategy != PDEIP_SEG_GREEDY && strategy != PDEIP_SEG_INVERSE)
+        return set_err(PDEIP_ERR_ARG, "%s: no such competition strategy (%d)", who, strategy);
+    return PDEIP_OK;
+}
+
+int check_level(const char *who, int nrows, int ncols, int S, int order, int strategy, double minCOV, float ransac_cset, int iterations,
+                double srem_thr, const SegPrm &p)
+{
+    RC(check_planes(who, nrows, ncols, S));
+    if (order != 1 && order != 2) return set_err(PDEIP_ERR_ARG, "%s: only 1st and 2nd order polynomials are implemented (order = %d)", who, order);
+    RC(check_strategy(who, strategy));
+    if (!std::isfinite(minCOV) || !std::isfinite(srem_thr) || !std::isfinite(p.err_thr) || !std::isfinite(ransac_cset))
+        return set_err(PDEIP_ERR_ARG, "%s: minCOV, srem_thr, err_thr and ransac_cset must be finite", who);
+    if (minCOV <= 0.0) return set_err(PDEIP_ERR_ARG, "%s: minCOV must be > 0 (got %g)", who, minCOV);
+    if (iterations < 0) return set_err(PDEIP_ERR_ARG, "%s: iterations must be >= 0 (got %d)", who, iterations);
+    return PDEIP_OK;
+}
+
+inline int tiles_of(int npix) { return (npix + SG_BLOCK - 1) / SG_BLOCK; }
+
+int launch_sizes(hipStream_t s, const float *PHI, int npix, int S, int *part, int *sizes)
+{
+    const int tiles = tiles_of(npix);
+    hipLaunchKernelGGL(k_seg_sizes, dim3((unsigned)tiles, (unsigned)S), dim3(SG_BLOCK), 0, s, PHI, npix, tiles, part);
+    hipLaunchKernelGGL(k_seg_sizes_final, dim3((unsigned)S), dim3(SG_FIN_BLOCK), 0, s, part, tiles, sizes);
+    HIPCHK(hipGetLastError());
+    return PDEIP_OK;
+}
+
+int launch_variance(hipStream_t s, const float *PHI, const float *dist, int npix, int S, double minCOV, double dist_cap, double *psum, int *pcnt,
+                    double *cov, int *n_out)
+{
+    const int tiles = tiles_of(npix);
+    hipLaunchKernelGGL(k_seg_variance, dim3((unsigned)tiles, (unsigned)S), dim3(SG_BLOCK), 0, s, PHI, dist, npix, tiles, std::isfinite(dist_cap) ? 1 : 0,
+                       dist_cap, psum, pcnt);
+    hipLaunchKernelGGL(k_seg_variance_final, dim3(1), dim3(SG_FIN_BLOCK), 0, s, psum, pcnt, tiles, S, minCOV, cov, n_out);
+    HIPCHK(hipGetLastError());
+    return PDEIP_OK;
+}
+
+int launch_data(hipStream_t s, const float *dist, const float *PHI, const float *DH, const double *cov, int npix, int S, int strategy, float *DATA,
+                double *P_out)
+{
+    const dim3 grid((unsigned)tiles_of(npix)), blk(SG_BLOCK);
+    if (strategy == PDEIP_SEG_SURFACE) hipLaunchKernelGGL(k_seg_data<STRAT_SURFACE>, grid, blk, 0, s, dist, PHI, DH, cov, npix, S, DATA, P_out);
+    else if (strategy == PDEIP_SEG_GREEDY) hipLaunchKernelGGL(k_seg_data<STRAT_GREEDY>, grid, blk, 0, s, dist, PHI, DH, cov, npix, S, DATA, P_out);
+    else hipLaunchKernelGGL(k_seg_data<STRAT_INVERSE>, grid, blk, 0, s, dist, PHI, DH, cov, npix, S, DATA, P_out);
+    HIPCHK(hipGetLastError());
+    return PDEIP_OK;
+}
+
+// Partials of the stage calls: [S * tiles] doubles, then as many ints.
+int stage_ws(int npix, int S, double **psum, int **pcnt)
+{
+    const size_t np = (size_t)S * tiles_of(npix);
+    float *ws = nullptr;
+    RC(ws_get(WS_SEG_STAGE, (2 * np + pad4(np)) * sizeof(float), &ws));
+    *psum = reinterpret_cast<double *>(ws);
+    *pcnt = reinterpret_cast<int *>(ws + 2 * np);
+    return PDEIP_OK;
+}
+
+// The pinned words the level reads the sizes back through, grown on demand and kept for the life of the process.
+int *g_pinned = nullptr;
+int g_pinned_cap = 0;
+int pinned_sizes(int S, int **out)
+{
+    if (S > g_pinned_cap) {
+        if (g_pinned) HIPCHK(hipHostFree(g_pinned));
+        g_pinned = nullptr;
+        g_pinned_cap = 0;
+        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&g_pinned), (size_t)std::max(S, 64) * sizeof(int), hipHostMallocDefault));
+        g_pinned_cap = std::max(S, 64);
+    }
+    *out = g_pinned;
+    return PDEIP_OK;
+}
+
+} // namespace
+
+extern "C" int pdeip_seg_sizes_dev(void *stream, const float *PHI, int nrows, int ncols, int S, int *sizes_out)
+{
+    const char *who = "pdeip_seg_sizes_dev";
+    NONNULL(who, PHI); NONNULL(who, sizes_out);
+    RC(check_planes(who, nrows, ncols, S));
+    double *psum = nullptr;
+    int *part = nullptr;
+    RC(stage_ws(nrows * ncols, S, &psum, &part));
+    RC(launch_sizes(static_cast<hipStream_t>(stream), PHI, nrows * ncols, S, part, sizes_out));
+    tls.last_launches = 2;
+    return PDEIP_OK;
+}
+
+extern "C" int pdeip_seg_variance_dev(void *stream, const float *PHI, const float *dist, int nrows, int ncols, int S, double minCOV, double dist_cap,
+                                      double *cov_out, int *n_out)
+{
+    const char *who = "pdeip_seg_variance_dev";
+    NONNULL(who, PHI); NONNULL(who, dist); NONNULL(who, cov_out);
+    RC(check_planes(who, nrows, ncols, S));
+    if (!std::isfinite(minCOV) || minCOV <= 0.0) return set_err(PDEIP_ERR_ARG, "%s: minCOV must be finite and > 0", who);
+    if (std::isnan(dist_cap)) dist_cap = std::numeric_limits<double>::infinity();
+    double *psum = nullptr;
+    int *pcnt = nullptr;
+    RC(stage_ws(nrows * ncols, S, &psum, &pcnt));
+    RC(launch_variance(static_cast<hipStream_t>(stream), PHI, dist, nrows * ncols, S, minCOV, dist_cap, psum, pcnt, cov_out, n_out));
+    tls.last_launches = 2;
+    return PDEIP_OK;
+}
+
+extern "C" int pdeip_seg_data_dev(void *stream, const float *dist, const float *PHI, const float *DH, const double *cov, int nrows, int ncols, int S,
+                                  int strategy, float *DATA_out, double *P_out)
+{
+    const char *who = "pdeip_seg_data_dev";
+    NONNULL(who, dist); NONNULL(who, PHI); NONNULL(who, DH); NONNULL(who, cov); NONNULL(who, DATA_out);
+    RC(check_planes(who, nrows, ncols, S));
+    RC(check_strategy(who, strategy));
+    if (DATA_out == dist || DATA_out == PHI || DATA_out == DH) return set_err(PDEIP_ERR_ARG, "%s: DATA_out must not alias an input", who);
+    RC(launch_data(static_cast<hipStream_t>(stream), dist, PHI, DH, cov, nrows * ncols, S, strategy, DATA_out, P_out));
+    tls.last_launches = 1;
+    return PDEIP_OK;
+}
+
+extern "C" int pdeip_seg_label_dev(void *stream, const float *PHI, int nrows, int ncols, int S, int *SEG_out)
+{
+    const char *who = "pdeip_seg_label_dev";
+    NONNULL(who, PHI); NONNULL(who, SEG_out);
+    RC(check_planes(who, nrows, ncols, S));
+    const int npix = nrows * ncols;
+    hipLaunchKernelGGL(k_seg_label, dim3((unsigned)tiles_of(npix)), dim3(SG_BLOCK), 0, static_cast<hipStream_t>(stream), PHI, npix, S, SEG_out);
+    HIPCHK(hipGetLastError());
+    tls.last_launches = 1;
+    return PDEIP_OK;
+}
+
+extern "C" int pdeip_seg_label(const float *PHI, int nrows, int ncols, int S, int *SEG_out)
+{
+    const char *who = "pdeip_seg_label";
+    NONNULL(who, PHI); NONNULL(who, SEG_out);
+    RC(check_planes(who, nrows, ncols, S));
+    RC(use_device());
+    const size_t n = (size_t)nrows * ncols;
+    float *ar = nullptr;
+    RC(ws_get(WS_ARENA, (pad4(n * S) + pad4(n)) * sizeof(float), &ar));
+    int *dSeg = reinterpret_cast<int *>(ar + pad4(n * S));
+    HIPCHK(hipMemcpy(ar, PHI, n * S * sizeof(float), hipMemcpyHostToDevice));
+    RC(pdeip_seg_label_dev(nullptr, ar, nrows, ncols, S, dSeg));
+    HIPCHK(hipMemcpy(SEG_out, dSeg, n * sizeof(int), hipMemcpyDeviceToHost));
+    return PDEIP_OK;
+}
+
+// ---- one scale: `iterations` competition iterations, resident ----------------------------------------------------------------------
+extern "C" int pdeip_seg_competition_level_dev(void *stream, const float *PHI, const float *D, int nrows, int ncols, int S, int order, int strategy,
+                                               double minCOV, float ransac_cset, int iterations, double srem_thr, unsigned long long seed,
+                                               unsigned long long *fit_counter, const pdeip_seg_params *prm, int *S_out, float *PHI_out,
+                                               float *surf_out, int *kept_out, double *cov_out)
+{
+    const char *who = "pdeip_seg_competition_level_dev";
+    tls.err[0] = '\0'; // a call that succeeds leaves pdeip_last_error() empty
+    NONNULL(who, PHI); NONNULL(who, D); NONNULL(who, S_out); NONNULL(who, PHI_out); NONNULL(who, surf_out); NONNULL(who, kept_out);
+    const SegPrm p = seg_resolve(prm);
+    RC(check_level(who, nrows, ncols, S, order, strategy, minCOV, ransac_cset, iterations, srem_thr, p));
+    if (PHI_out == PHI) return set_err(PDEIP_ERR_ARG, "%s: PHI_out must not alias PHI", who);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int npix = nrows * ncols, ncoef = order == 1 ? 3 : 6, tiles = tiles_of(npix);
+    const size_t np = (size_t)S * tiles, nS = pad4((size_t)S * npix);
+    const float nu = (float)(p.gamma_coef * std::pow((double)nrows * (double)ncols, 0.7));
+    const double remove_below = srem_thr * (double)nrows * (double)ncols;
+
+    // workspace: the doubles first (8-byte aligned: a hipMalloc'd base, every offset a multiple of 4 floats)
+    float *ws = nullptr;
+    const size_t nDbl = pad4(2 * (np + (size_t)S));
+    RC(ws_get(WS_SEG, (nDbl + 2 * pad4(np) + pad4((size_t)S) + pad4((size_t)S * ncoef) + pad4((size_t)npix) + 6 * nS) * sizeof(float), &ws));
+    double *psum = reinterpret_cast<double *>(ws), *cov = psum + np;
+    int *pcnt = reinterpret_cast<int *>(ws + nDbl), *part = pcnt + pad4(np), *sizes = part + pad4(np);
+    float *models = reinterpret_cast<float *>(sizes + pad4((size_t)S));
+    float *Dfill = models + pad4((size_t)S * ncoef);
+    float *cur = Dfill + pad4((size_t)npix), *nxt = cur + nS, *DATA = nxt + nS, *DH = DATA + nS, *GRAD = DH + nS, *DIST = GRAD + nS;
+    int *host_sizes = nullptr;
+    RC(pinned_sizes(S, &host_sizes));
+
+    int launches = 0;
+    RC(copy_d2d(s, cur, PHI, (size_t)S * npix));
+    const float *Dsrc = D;
+    if (!std::isnan(p.nan_fill)) {
+        hipLaunchKernelGGL(k_seg_nanfill, dim3((unsigned)tiles), dim3(SG_BLOCK), 0, s, D, npix, p.nan_fill, Dfill);
+        HIPCHK(hipGetLastError());
+        Dsrc = Dfill;
+        launches++;
+    }
+    HIPCHK(hipMemsetAsync(models, 0, (size_t)S * ncoef * sizeof(float), s));
+    HIPCHK(hipMemsetAsync(cov, 0, (size_t)S * sizeof(double), s));
+
+    std::vector<int> kept((size_t)S);
+    for (int k = 0; k < S; k++) kept[k] = k;
+    int live = S;
+    bool recalc = false;
+    unsigned long long fit = fit_counter ? *fit_counter : 0ull;
+    for (int it = 1; it <= iterations; it++) {
+        // 1. sizes, read back once (the removal decides the shapes of everything after it)
+        RC(launch_sizes(s, cur, npix, live, part, sizes));
+        HIPCHK(hipMemcpyAsync(host_sizes, sizes, (size_t)live * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        launches += 2;
+        int n_kept = 0;
+        for (int k = 0; k < live; k++) {
+            if ((double)host_sizes[k] < remove_below) continue;
+            if (n_kept != k) { // survivors move down in order: the destination plane is always below its source
+                RC(copy_d2d(s, cur + (size_t)n_kept * npix, cur + (size_t)k * npix, (size_t)npix));
+                launches++;
+            }
+            kept[n_kept++] = kept[k];
+        }
+        if (n_kept != live) {
+            live = n_kept;
+            recalc = true;
+            if (live == 0) break;
+            HIPCHK(hipMemsetAsync(models, 0, (size_t)S * ncoef * sizeof(float), s)); // ALL the models, as the .m does
+        }
+        // 2. the terms
+        if ((it & 1) || recalc) {
+            RC(pdeip_cv_terms_dev(s, cur, nrows, ncols, live, p.c0, p.c1, p.dh_floor, DH, GRAD));
+            launches += 1;
+            for (int k = 0; k < live; k++) {
+                float *M = models + (size_t)k * ncoef;
+                RC(pdeip_surface_fit_masked_dev(s, cur + (size_t)k * npix, Dsrc, nrows, ncols, order, M, p.err_thr, ransac_cset, 10, nullptr,
+                                                seed + 65536ull * fit, M, DIST + (size_t)k * npix, nullptr));
+                launches += tls.last_launches;
+                fit++;
+            }
+            RC(launch_variance(s, cur, DIST, npix, live, minCOV, p.dist_cap, psum, pcnt, cov, nullptr));
+            RC(launch_data(s, DIST, cur, DH, cov, npix, live, strategy, DATA, nullptr));
+            launches += 3;
+            recalc = false;
+        }
+        // 3. the step
+        RC(pdeip_cv_solver_dev(s, cur, DATA, DH, GRAD, nrows, ncols, live, 1.0f, nu, nxt));
+        launches += tls.last_launches;
+        std::swap(cur, nxt);
+    }
+    if (fit_counter) *fit_counter = fit;
+    *S_out = live;
+    for (int k = 0; k < live; k++) kept_out[k] = kept[k];
+    if (live > 0) {
+        RC(copy_d2d(s, PHI_out, cur, (size_t)live * npix));
+        RC(copy_d2d(s, surf_out, models, (size_t)live * ncoef));
+        if (cov_out) RC(copy_d2d(s, reinterpret_cast<float *>(cov_out), reinterpret_cast<const float *>(cov), 2 * (size_t)live));
+        launches += 3;
+    }
+    tls.last_launches = launches;
+    return PDEIP_OK;
+}
+
+extern "C" int pdeip_seg_competition_level(const float *PHI, const float *D, int nrows, int ncols, int S, int order, int strategy, double minCOV,
+                                           float ransac_cset, int iterations, double srem_thr, unsigned long long seed,
+                                           unsigned long long *fit_counter, const pdeip_seg_params *prm, int *S_out, float *PHI_out,
+                                           float *surf_out, int *kept_out, double *cov_out)
+{
+    const char *who = "pdeip_seg_competition_level";
+    tls.err[0] = '\0'; // a call that succeeds leaves pdeip_last_error() empty
+    NONNULL(who, PHI); NONNULL(who, D); NONNULL(who, S_out); NONNULL(who, PHI_out); NONNULL(who, surf_out); NONNULL(who, kept_out);
+    const SegPrm p = seg_resolve(prm);
+    RC(check_level(who, nrows, ncols, S, order, strategy, minCOV, ransac_cset, iterations, srem_thr, p));
+    RC(use_device());
+    const size_t n = (size_t)nrows * ncols, nS = pad4(n * S);
+    const int ncoef = order == 1 ? 3 : 6;
+    float *ar = nullptr;
+    RC(ws_get(WS_ARENA, (pad4(2 * (size_t)S) + 2 * nS + pad4(n) + pad4((size_t)S * ncoef)) * sizeof(float), &ar));
+    double *dCov = reinterpret_cast<double *>(ar);
+    float *dP = ar + pad4(2 * (size_t)S), *dO = dP + nS, *dD = dO + nS, *dM = dD + pad4(n);
+    HIPCHK(hipMemcpy(dP, PHI, n * S * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dD, D, n * sizeof(float), hipMemcpyHostToDevice));
+    RC(pdeip_seg_competition_level_dev(nullptr, dP, dD, nrows, ncols, S, order, strategy, minCOV, ransac_cset, iterations, srem_thr, seed, fit_counter,
+                                       prm, S_out, dO, dM, kept_out, dCov));
+    const int live = *S_out;
+    if (live > 0) {
+        HIPCHK(hipMemcpy(PHI_out, dO, n * live * sizeof(float), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(surf_out, dM, (size_t)live * ncoef * sizeof(float), hipMemcpyDeviceToHost));
+        if (cov_out) HIPCHK(hipMemcpy(cov_out, dCov, (size_t)live * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    return PDEIP_OK;
+}
+
+// ---- regionCompetition(): the D pyramid, the visits [1..K, K..1], PHI carried from visit to visit --------------------------------
+extern "C" int pdeip_region_competition(const float *D, const float *PHI, int nrows, int ncols, int S, int order, int strategy, double sigmaLim,
+                                        float ransac_cset, int iterations, double srem_thr, double scl_factor, double rc_scl, unsigned long long seed,
+                                        const pdeip_seg_params *prm, int *S_out, float *PHI_out, float *surf_out, int *kept_out)
+{
+    const char *who = "pdeip_region_competition";
+    tls.err[0] = '\0'; // a call that succeeds leaves pdeip_last_error() empty
+    NONNULL(who, D); NONNULL(who, PHI); NONNULL(who, S_out); NONNULL(who, PHI_out); NONNULL(who, surf_out); NONNULL(who, kept_out);
+    const SegPrm p = seg_resolve(prm);
+    RC(check_level(who, nrows, ncols, S, order, strategy, sigmaLim, ransac_cset, iterations, srem_thr, p));
+    if (!(scl_factor > 0.0 && scl_factor < 1.0)) return set_err(PDEIP_ERR_ARG, "%s: scl_factor must lie in (0, 1) (got %g)", who, scl_factor);
+    if (!(rc_scl > 0.0) || !std::isfinite(rc_scl)) return set_err(PDEIP_ERR_ARG, "%s: rc_scl must be finite and > 0 (got %g)", who, rc_scl);
+    if (nrows < 3 || ncols < 3) return set_err(PDEIP_ERR_ARG, "%s: D must be at least 3x3 (got %dx%d)", who, nrows, ncols);
+    // scales: size(imresize(D, scl_factor)) = ceil(size * scl_factor) while both sides stay >= rc_scl x the original
+    std::vector<std::pair<int, int>> sz{{nrows, ncols}};
+    for (;;) {
+        const int r = (int)std::ceil(sz.back().first * scl_factor), c = (int)std::ceil(sz.back().second * scl_factor);
+        if (!((double)r >= nrows * rc_scl && (double)c >= ncols * rc_scl) || r < 3 || c < 3) break;
+        if (r == sz.back().first && c == sz.back().second) break; // a size that no longer shrinks ends the pyramid
+        sz.push_back({r, c});
+    }
+    const int K = (int)sz.size(), ncoef = order == 1 ? 3 : 6;
+    RC(use_device());
+    const size_t n0 = (size_t)nrows * ncols, nS = pad4(n0 * S);
+    size_t nD = 0;
+    for (auto &q : sz) nD += pad4((size_t)q.first * q.second);
+    float *ws = nullptr;
+    RC(ws_get(WS_SEG_RC, (nD + 2 * nS + pad4((size_t)S * ncoef)) * sizeof(float), &ws));
+    std::vector<float *> Dp((size_t)K);
+    float *at = ws;
+    for (int k = 0; k < K; k++) {
+        Dp[k] = at;
+        at += pad4((size_t)sz[k].first * sz[k].second);
+    }
+    float *A = at, *B = A + nS, *dM = B + nS;
+    HIPCHK(hipMemcpy(Dp[0], D, n0 * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(A, PHI, n0 * S * sizeof(float), hipMemcpyHostToDevice));
+    for (int k = 1; k < K; k++)
+        RC(pdeip_pyr_resize_dev(nullptr, Dp[k - 1], sz[k - 1].first, sz[k - 1].second, 1, sz[k].first, sz[k].second, 1, Dp[k]));
+
+    std::vector<int> visits;
+    for (int k = 0; k < K; k++) visits.push_back(k);
+    for (int k = K - 1; k >= 0; k--) visits.push_back(k);
+    std::vector<int> kept((size_t)S), kv((size_t)S);
+    for (int k = 0; k < S; k++) kept[k] = k;
+    int live = S;
+    unsigned long long fit = 0;
+    for (size_t v = 0; v < visits.size(); v++) {
+        const int k = visits[v], r = sz[k].first, c = sz[k].second;
+        int out = 0;
+        RC(pdeip_seg_competition_level_dev(nullptr, A, Dp[k], r, c, live, order, strategy, sigmaLim, ransac_cset, iterations, srem_thr, seed, &fit, prm,
+                                           &out, B, dM, kv.data(), nullptr));
+        for (int i = 0; i < out; i++) kept[i] = kept[kv[i]];
+        live = out;
+        if (live == 0) break;
+        if (v + 1 < visits.size()) {
+            const int kn = visits[v + 1];
+            RC(pdeip_pyr_resize_dev(nullptr, B, r, c, live, sz[kn].first, sz[kn].second, 1, A));
+        }
+    }
+    *S_out = live;
+    for (int i = 0; i < live; i++) kept_out[i] = kept[i];
+    if (live > 0) {
+        HIPCHK(hipMemcpy(PHI_out, B, n0 * live * sizeof(float), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(surf_out, dM, (size_t)live * ncoef * sizeof(float), hipMemcpyDeviceToHost));
+    } else {
+        HIPCHK(hipDeviceSynchronize());
+    }
+    return PDEIP_OK;
+}

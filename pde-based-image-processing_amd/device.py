@@ -586,3 +586,103 @@ def pyr_smooth(I, G):
     out = torch.empty_like(I)
     capi.call("pdeip_pyr_smooth_dev", _stream(), I.data_ptr(), nrows, ncols, F, g.ctypes.data, int(g.shape[0]), out.data_ptr())
     return out
+
+
+# ---- region competition: the segmentation drivers' inner loop (csrc/pdeip_segmentation.hip; the contract: include/pdeip.h) ----
+
+class SegParams(ctypes.Structure):
+    """pdeip_seg_params: NaN keeps the dense driver's value; SegParams.sparse() is DispSegmentationSparse.m's form."""
+    _fields_ = [(k, ctypes.c_double) for k in ("c0", "c1", "dh_floor", "err_thr", "gamma_coef", "dist_cap", "nan_fill")]
+
+    @classmethod
+    def make(cls, sparse=False, **param):
+        vals = dict(c0=2.0, c1=4.0, dh_floor=0.04, err_thr=1.2, gamma_coef=0.005, dist_cap=100.0, nan_fill=1000.0) if sparse else {}
+        for k, v in param.items():
+            if k not in dict(cls._fields_):
+                raise TypeError("unknown segmentation parameter %r" % k)
+            vals[k] = float(v)
+        return cls(*[vals.get(k, float("nan")) for k, _ in cls._fields_])
+
+
+SEG_STRATEGIES = {"surface": capi.SEG_SURFACE, "greedy": capi.SEG_GREEDY, "inverse": capi.SEG_INVERSE}
+
+
+def _strategy(competition):
+    if competition not in SEG_STRATEGIES:
+        raise capi.PdeipError(capi.PDEIP_ERR_ARG, "No such competition strategy! (%r)" % (competition,))
+    return SEG_STRATEGIES[competition]
+
+
+def _chk_typed(t, dtype, n, what):
+    if t.dtype != dtype or not t.is_cuda or not t.is_contiguous() or t.numel() < n:
+        raise capi.PdeipError(capi.PDEIP_ERR_ARG, "%s must be a contiguous %s CUDA tensor of at least %d elements" % (what, dtype, n))
+
+
+def seg_sizes(PHI, sizes_out):
+    """sizes_out[s] = #{PHI_s >= 0}: PHI [S, ncols, nrows], sizes_out int32 [S].  Nothing is read back."""
+    _chk(PHI)
+    nrows, ncols, S = _dims(PHI)
+    _chk_typed(sizes_out, torch.int32, S, "seg_sizes: sizes_out")
+    capi.call("pdeip_seg_sizes_dev", _stream(), PHI.data_ptr(), nrows, ncols, S, sizes_out.data_ptr())
+
+
+def seg_variance(PHI, dist, minCOV, dist_cap, cov_out, n_out=None):
+    """cov_out[s] = max(mean of dist over PHI_s >= 0 (and dist < dist_cap when that is finite), minCOV) in float64; cov_out float64
+    [S], n_out int32 [S] or None."""
+    _chk(PHI, dist)
+    nrows, ncols, S = _dims(PHI)
+    if dist.shape != PHI.shape:
+        raise capi.PdeipError(capi.PDEIP_ERR_ARG, "seg_variance: dist must have PHI's shape")
+    _chk_typed(cov_out, torch.float64, S, "seg_variance: cov_out")
+    if n_out is not None:
+        _chk_typed(n_out, torch.int32, S, "seg_variance: n_out")
+    capi.call("pdeip_seg_variance_dev", _stream(), PHI.data_ptr(), dist.data_ptr(), nrows, ncols, S, float(minCOV), float(dist_cap),
+              cov_out.data_ptr(), n_out.data_ptr() if n_out is not None else None)
+
+
+def seg_data(dist, PHI, DH, cov, competition, DATA_out, P_out=None):
+    """The likelihood, competitor and log-odds planes: DATA_out float32 like PHI; P_out float64 like PHI or None; cov float64 [S]."""
+    _chk(dist, PHI, DH, DATA_out)
+    nrows, ncols, S = _dims(PHI)
+    if not (dist.shape == PHI.shape == DH.shape == DATA_out.shape):
+        raise capi.PdeipError(capi.PDEIP_ERR_ARG, "seg_data: dist, PHI, DH and DATA_out must have one shape")
+    _chk_typed(cov, torch.float64, S, "seg_data: cov")
+    if P_out is not None:
+        _chk_typed(P_out, torch.float64, PHI.numel(), "seg_data: P_out")
+    capi.call("pdeip_seg_data_dev", _stream(), dist.data_ptr(), PHI.data_ptr(), DH.data_ptr(), cov.data_ptr(), nrows, ncols, S,
+              _strategy(competition), DATA_out.data_ptr(), P_out.data_ptr() if P_out is not None else None)
+
+
+def seg_competition_level(PHI, D, order, minCOV, ransac_cset, iterations, srem_thr, competition="inverse", seed=0, fit_counter=0, prm=None):
+    """`iterations` competition iterations on one scale (pdeip_seg_competition_level_dev): PHI [S, ncols, nrows], D [ncols, nrows].
+    Returns (PHI_out [S_out, ncols, nrows], surf [S_out, ncoef], kept (list of input indices), cov float64 [S_out], fit_counter
+    after the call).  The call synchronises the stream once per iteration (the sizes decide removal on the host)."""
+    _chk(PHI, D)
+    if PHI.dim() != 3 or D.shape != PHI.shape[1:]:
+        raise capi.PdeipError(capi.PDEIP_ERR_ARG, "seg_competition_level: PHI must be [S, ncols, nrows] and D [ncols, nrows]")
+    nrows, ncols, S = _dims(PHI)
+    ncoef = 6 if order == 2 else 3
+    out = torch.empty_like(PHI)
+    surf = torch.zeros((S, ncoef), dtype=torch.float32, device=PHI.device)
+    cov = torch.zeros(S, dtype=torch.float64, device=PHI.device)
+    s_out = ctypes.c_int(0)
+    kept = (ctypes.c_int * S)()
+    fit = ctypes.c_ulonglong(int(fit_counter))
+    prm = prm if prm is not None else SegParams.make()
+    capi.call("pdeip_seg_competition_level_dev", _stream(), PHI.data_ptr(), D.data_ptr(), nrows, ncols, S, int(order), _strategy(competition),
+              float(minCOV), float(ransac_cset), int(iterations), float(srem_thr), ctypes.c_ulonglong(int(seed) & ((1 << 64) - 1)),
+              ctypes.addressof(fit), ctypes.addressof(prm), ctypes.addressof(s_out), out.data_ptr(), surf.data_ptr(), ctypes.addressof(kept),
+              cov.data_ptr())
+    n = s_out.value
+    return out[:n], surf[:n], [int(k) for k in kept[:n]], cov[:n], int(fit.value)
+
+
+def seg_label(PHI, SEG_out=None):
+    """The numbered map: sum of s*[PHI_s > 0] over 1-based s, 0 where segments overlap; int32 [ncols, nrows]."""
+    _chk(PHI)
+    nrows, ncols, S = _dims(PHI)
+    if SEG_out is None:
+        SEG_out = torch.empty(PHI.shape[-2:], dtype=torch.int32, device=PHI.device)
+    _chk_typed(SEG_out, torch.int32, nrows * ncols, "seg_label: SEG_out")
+    capi.call("pdeip_seg_label_dev", _stream(), PHI.data_ptr(), nrows, ncols, S, SEG_out.data_ptr())
+    return SEG_out

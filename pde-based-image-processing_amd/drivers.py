@@ -14,6 +14,8 @@ capi.MODE_RED_BLACK the parallel one).
     TVdenoise8 / TVdenoise4     matlab/denoising/TVdenoise{8,4}.m                 total-variation denoising
     GAC_v10a / GAC_v10b         matlab/active_contour/GAC_v10{a,b}.m              geodesic active contours (C++ only: pdeip_gac)
     Diffusion4_v10              matlab/diffusion/Diffusion4_v10.m                 nonlinear diffusion (C++ only: pdeip_diffusion4)
+    regionCompetition           matlab/segmentation/DispSegmentation.m:448-654    region competition of the segmentation drivers
+    segments_numbered           matlab/segmentation/DispSegmentation.m:190-198    (C++ only: pdeip_region_competition, pdeip_seg_label)
 
 `Us=`, `Vs=` (param.Us / param.Vs: spatial a-priori fields, double, NaN = no constraint) and `scales=` (param.scales) are taken
 by the late-linearisation flow drivers and the disparity driver as the reference's drivers take them.
@@ -528,3 +530,50 @@ def SurfaceEquation(A, B, M_in, err_thr, min_set_size, iter, seed=None, sets=Non
         raise ValueError("SurfaceEquation: M_in must have as many elements as A has columns")
     M, err, _, _ = mex_api.surface_equation(A, B, M_in, float(np.float32(err_thr)), float(np.float32(min_set_size)), int(iter), seed, sets)
     return np.asfortranarray(M.reshape(-1, 1)), np.asfortranarray(err.reshape(-1, 1))
+
+
+def _planes3(PHI):
+    P = np.asarray(PHI, dtype=np.float32)
+    if P.ndim == 2:
+        P = P[:, :, None]
+    if P.ndim != 3 or P.shape[2] < 1:
+        raise ValueError("PHI must be [rows, cols, segments] with at least one segment (got %s)" % (P.shape,))
+    return np.asfortranarray(P)
+
+
+def regionCompetition(D, PHI, polyorder, sigmaLim, ransac_cset, iterations, srem_thr, competition="inverse", sparse=False, seed=0,
+                      scl_factor=0.7, rc_scl=0.4, **param):
+    """[PHIout SParam] = regionCompetition(D, pyramid, polyorder, sigmaLim, ransac_cset, iterations, srem_thr, PHIin, competition)
+    of matlab/segmentation/DispSegmentation.m (sparse=True: DispSegmentationSparse.m's constants) in one pdeip_region_competition
+    call: the D pyramid (scl_factor, rc_scl as the drivers' param struct names them), the visits down and up, every iteration
+    resident.  param overrides single constants (c0, c1, dh_floor, err_thr, gamma_coef, dist_cap, nan_fill).  Returns (PHI [rows,
+    cols, S_out], SParam [ncoef, S_out], kept: the 0-based input index of each surviving segment)."""
+    import ctypes
+
+    prm = dev.SegParams.make(sparse=sparse, **param)
+    Dm = np.asfortranarray(np.asarray(D, dtype=np.float32))
+    P = _planes3(PHI)
+    rows, cols, S = P.shape
+    if Dm.shape != (rows, cols):
+        raise ValueError("regionCompetition: D is %s but PHI is %s" % (Dm.shape, P.shape))
+    ncoef = 6 if polyorder == 2 else 3
+    out = np.zeros(P.shape, np.float32, order="F")
+    surf = np.zeros((ncoef, S), np.float32, order="F")
+    kept = (ctypes.c_int * S)()
+    s_out = ctypes.c_int(0)
+    capi.call("pdeip_region_competition", Dm.ctypes.data, P.ctypes.data, rows, cols, S, int(polyorder), dev._strategy(competition),
+              float(sigmaLim), float(ransac_cset), int(iterations), float(srem_thr), float(scl_factor), float(rc_scl),
+              ctypes.c_ulonglong(int(seed) & ((1 << 64) - 1)), ctypes.addressof(prm), ctypes.addressof(s_out), out.ctypes.data,
+              surf.ctypes.data, ctypes.addressof(kept))
+    n = s_out.value
+    return np.asfortranarray(out[:, :, :n]), np.asfortranarray(surf[:, :n]), [int(k) for k in kept[:n]]
+
+
+def segments_numbered(PHI):
+    """The numbered segment map the drivers return (DispSegmentation.m:190-198): s where only segment s (1-based) has PHI > 0, 0
+    where none or several have; int32 [rows, cols], one pdeip_seg_label call."""
+    P = _planes3(PHI)
+    rows, cols, S = P.shape
+    out = np.zeros((rows, cols), np.int32, order="F")
+    capi.call("pdeip_seg_label", P.ctypes.data, rows, cols, S, out.ctypes.data)
+    return out
