@@ -798,6 +798,105 @@ int pdeip_region_competition(const float *D, const float *PHI, int nrows, int nc
 int pdeip_seg_label_dev(void *stream, const float *PHI, int nrows, int ncols, int S, int *SEG_out);
 int pdeip_seg_label(const float *PHI, int nrows, int ncols, int S, int *SEG_out);
 
+/* ---- connected components (csrc/pdeip_ccl.hip) ------------------------------------------------------------------------------
+ * [L, num] = bwlabel(A > 0, conn) and regionprops(.., 'Area') as generateSeeds() calls them (matlab/segmentation/
+ * DispSegmentation.m:282-298).  A [nrows x ncols] column-major float32; a pixel is foreground iff A > 0: a NaN, +0.0, -0.0 and
+ * every negative value are background, a positive subnormal and +Inf are foreground.  conn is 8 (bwlabel's default, what the
+ * drivers use: diagonal contacts join) or 4.  The numbering is MATLAB's: components are numbered 1..num in the order of their
+ * first pixel in column-major (memory) order, background is 0.  L_out int32 [nrows x ncols] (must not alias A); num_out int [1];
+ * areas_out (NULL ok) int [areas_cap]: areas_out[l-1] = the pixel count of component l for l <= min(num, areas_cap), 0 for the
+ * entries from num on; areas beyond areas_cap are not written.  The result is a pure function of the mask: the implementation
+ * uses integer atomics only (min on labels, adds on areas), whose outcome is unique, and no floating-point atomics; two calls give
+ * the same bits.
+ *   Two forms, chosen by the plane's size: planes of up to 16384 pixels (the coarse pyramid scales the drivers label) are done by
+ * one workgroup in LDS in one launch; larger ones tile by tile in LDS, then the tile seams, then a prefix sum over the roots.
+ * PDEIP_CCL_SMALL=0 forces the tiled form, =1 the one-workgroup form wherever it admits the plane.
+ *   Refused with PDEIP_ERR_ARG before any HIP call: a NULL A, L_out / out or (bwlabel) num_out, nrows or ncols < 1, nrows*ncols >
+ * INT_MAX, conn not 4 or 8, areas_cap < 0.  pdeip_set_mode does not apply.
+ *   The _dev forms take device pointers (num_out and areas_out too), are asynchronous on `stream`, take their workspace from the
+ * library's cache, run a number of launches that depends on the plane's size only and read nothing back: graph-capturable.
+ * The tiled form keeps its tree, labels, areas and scalars in ONE workspace of that cache, as the other units do: two _dev calls
+ * on different streams, or a captured graph replayed while another call of this section runs, would share it and race.  Order
+ * such calls on one stream. */
+int pdeip_bwlabel_dev(void *stream, const float *A, int nrows, int ncols, int conn, int *L_out, int *num_out, int *areas_out,
+                      int areas_cap);
+int pdeip_bwlabel(const float *A, int nrows, int ncols, int conn, int *L_out, int *num_out, int *areas_out, int areas_cap);
+/* out = lo everywhere and hi on the component with the largest area (DispSegmentation.m:284-290; [CCY CCI] = max(...): the LOWEST
+ * label wins a tie).  No foreground at all: all lo, *area_out = 0, *num_out = 0 (this library's definition; the .m indexes with an
+ * empty CCI there).  out float32 [nrows x ncols] may alias A.  num_out, area_out (NULL ok): the number of components and the
+ * largest area; device pointers in the _dev form.  Same forms, refusals and capturability as above. */
+int pdeip_largest_component_dev(void *stream, const float *A, int nrows, int ncols, int conn, float hi, float lo, float *out,
+                                int *num_out, int *area_out);
+int pdeip_largest_component(const float *A, int nrows, int ncols, int conn, float hi, float lo, float *out, int *num_out,
+                            int *area_out);
+
+/* ---- generateSeeds() and the dense driver (csrc/pdeip_segmentation.hip) --------------------------------------------------------
+ * [PHIout SParam] = generateSeeds(Din, pyramid, polyorder, sigmaLim, ransac_cset_vect, iterations, srem_thr, AAin, seeds)
+ * (matlab/segmentation/DispSegmentation.m:203-443) in one call, host pointers, resident on the device for the whole call, with
+ * the definitions fixed above for regionCompetition().  D [nrows x ncols]; AA [nrows x ncols] float or NULL for all ones, a NaN
+ * counts as 0; cset_vect double [n_cset].
+ *   Scales: the sizes follow the rule of pdeip_region_competition with pyr_scl in place of rc_scl; the D pyramid is built through
+ * pdeip_pyr_resize_dev(cubic); the visits are [1..K, K..1], numbered v = 0..2K-1.  gamma starts at 0.01 per call.
+ *   Per seed: the AA pyramid is formed by cubic resize to each scale's size; minCOV = sigmaLim; PHI_1 = -1 everywhere and +1 at the
+ * 0-based rows 1, 6, 11, .. <= nrows-2 and columns 1, 6, .. <= ncols-2.
+ *   Per visit: include = AA_scl > 0.05f; at v = 0 PHI(~include) = -1; the model is reset to "none"; at v = K (the second visit of
+ * the coarsest scale) PHI = pdeip_largest_component_dev(PHI, 8, +5, -5); nu = (float)(gamma*(rows*cols)^0.7) in double.
+ *   Per iteration it = 1..iterations: RITER = (it == 1 && v == 0) ? 2000 : 100; RCONS = v == 0 ? cset_vect[min(it, n_cset) - 1] :
+ * cset_vect[n_cset - 1]; the count #{PHI >= 0} is read back, fewer than 20 marks the seed EMPTY and leaves both loops; the fit is
+ * pdeip_surface_fit_masked_dev with the current model (none on a visit's first iteration), err_thr 0.7, RCONS, RITER, the dist
+ * plane and seed + 65536*k, k the running count of all fits (starting at *fit_counter, 0 if NULL; the end value is returned there
+ * so that a caller can chain counts); cov as pdeip_seg_variance_dev with S = 1, floored at minCOV; DATA as pdeip_seg_data_dev
+ * with S = 1 and PDEIP_SEG_INVERSE (the -c*expm1(-t) form of c - P); DATA(~include) = -2; DH, gradPHI = pdeip_cv_terms_dev(1, 1,
+ * NaN); PHI = pdeip_cv_solver_dev(PHI, DATA, DH, gradPHI, 1, nu).
+ *   After a visit: EMPTY: gamma *= 0.8 (this persists over the remaining seeds) and the seed ends without output.  At v = K with
+ * iterations > 0: minCOV becomes the UNFLOORED variance of the visit's last iteration (its mask, its dist plane) if that exceeds
+ * mincov_gate (a NaN never does).  Otherwise PHI is resized (cubic) to the next visit's size.
+ *   After a seed that is not empty its PHI_1 and model are appended to PHI_out [nrows x ncols x seeds] (S_out planes written) and
+ * surf_out [ncoef x seeds] (NaN with iterations == 0: no fit was made); then AA_1 = (PHI_1 < 0) && (AA_1 != 0).
+ *   The .m's final "remove small segments" block (:435-443) operates on PHI{1}, which by then is PHIinitial, never on PHIout: it
+ * removes nothing.  This call removes nothing and takes no srem_thr.
+ *   pdeip_seeds_params: what the two drivers' generateSeeds() differ in; a NaN member (or prm == NULL) keeps the dense value:
+ * dist_cap +Inf (sparse 100), nan_fill NaN (sparse 1000: the fit and dist see D with its NaNs replaced), mincov_gate -Inf (sparse
+ * 0.5, DispSegmentationSparse.m:417-424).  err_thr is 0.7 in both.
+ *   trace (NULL ok) records what a checker needs: counts[0..min(n_counts, counts_cap)) every count read back, in order (n_counts is
+ * the number there were); largest (NULL ok) [rK x cK x seeds] the v = K largest-component planes, n_largest of them.
+ *   The count needs one pinned read-back per iteration, as the level call does: NOT graph-capturable.  Refused with PDEIP_ERR_ARG
+ * before any HIP call: a NULL D or output, nrows or ncols < 3, seeds outside 1..65535, planes too large, iterations < 0, order not
+ * 1 or 2, a non-finite or non-positive sigmaLim, n_cset < 1 or a non-finite entry, scl_factor outside (0, 1), pyr_scl not finite
+ * or <= 0.  pdeip_set_mode does not apply. */
+typedef struct pdeip_seeds_params {
+    double dist_cap, nan_fill, mincov_gate;
+} pdeip_seeds_params;
+typedef struct pdeip_seeds_trace {
+    int *counts;
+    int counts_cap, n_counts;
+    float *largest;
+    int n_largest;
+} pdeip_seeds_trace;
+int pdeip_generate_seeds(const float *D, const float *AA, int nrows, int ncols, int order, double sigmaLim, const double *cset_vect,
+                         int n_cset, int iterations, int seeds, double scl_factor, double pyr_scl, unsigned long long seed,
+                         unsigned long long *fit_counter, const pdeip_seeds_params *prm, pdeip_seeds_trace *trace, int *S_out,
+                         float *PHI_out, float *surf_out);
+/* [PHI SEG SParam] = DispSegmentation(Din, param) (DispSegmentation.m:31-198), host pointers.  NaNs of Din are set to 0;
+ * cset_vect = ransac_min_cset + (ransac_max_cset - ransac_min_cset)/ransac_cset_cycles * [0..cycles] (:56); strategy inverse.
+ *   PHIin == NULL (param.PHI empty): seeds (sigmaLim 0.7, 20 iterations, AA == 1 allowed or everything with AA == NULL, gen_scl);
+ * unless seeds == 1: competition (1.5, 30), seeds again (1.2, 20, rc_scl) on sum(PHI > 0, 3) == 0, concatenated, competition
+ * (1.5, 20).  PHIin [nrows x ncols x S_in] given: competition (1.0, 20), one more seed (1.2, 20, rc_scl) on the uncovered
+ * pixels, competition (2.0, 20).  The stages are pdeip_generate_seeds and pdeip_region_competition; stage j (0-based, in call
+ * order) draws from seed + j*2^32; PHI crosses the host between stages.  A stage after which no segment is left ends the call
+ * with *S_out = 0 and nothing else written (a seeding stage that only adds nothing to existing segments goes on, as cat(3, PHI,
+ * []) does).  PHI_out and surf_out must hold 2*seeds (PHIin == NULL) or S_in + 1 planes / models; *S_out of them are written;
+ * SEG_out int32 [nrows x ncols] through pdeip_seg_label.  A NaN (double) or 0 (int) member of prm, or prm == NULL, keeps the
+ * .m's default: srem_thr 0.002, polyorder 1, seeds 15, scl_factor 0.7, gen_scl 0.2, rc_scl 0.4, ransac_min_cset 0.1,
+ * ransac_max_cset 0.7, ransac_cset_cycles 10.  Refusals: those of the two stage calls, before any HIP call.  Not graph-capturable. */
+typedef struct pdeip_dispseg_params {
+    double srem_thr, scl_factor, gen_scl, rc_scl, ransac_min_cset, ransac_max_cset;
+    int polyorder, seeds, ransac_cset_cycles;
+} pdeip_dispseg_params;
+int pdeip_disp_segmentation(const float *Din, int nrows, int ncols, const float *PHIin, int S_in, const float *AA,
+                            const pdeip_dispseg_params *prm, unsigned long long seed, int *S_out, float *PHI_out, int *SEG_out,
+                            float *surf_out);
+
 #ifdef __cplusplus
 }
 #endif

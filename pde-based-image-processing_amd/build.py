@@ -31,7 +31,8 @@ UNITS = {
     "pdeip_levelset.hip": ["pdeip_levelset.hpp", "pdeip_cv.hpp"],
     "pdeip_diffusion.hip": ["pdeip_models.hpp", "pdeip_pointwise.hpp", "pdeip_diffusion.hpp"],
     "pdeip_ransac.hip": ["pdeip_ransac.hpp", "pdeip_reduce.hpp"],
-    "pdeip_segmentation.hip": ["pdeip_segmentation.hpp", "pdeip_reduce.hpp"],
+    "pdeip_segmentation.hip": ["pdeip_segmentation.hpp", "pdeip_reduce.hpp", "pdeip_seeds_plan.hpp"],
+    "pdeip_ccl.hip": ["pdeip_ccl.hpp", "pdeip_ccl_plan.hpp"],
 }
 # -ffp-contract=off is part of the parity contract (the reference is FMA-free C).
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]

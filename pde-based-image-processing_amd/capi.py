@@ -150,6 +150,15 @@ SIGNATURES = {
                                  ctypes.c_ulonglong, _P, _P, _P, _P, _P],
     "pdeip_seg_label_dev": [_P, _P, _I, _I, _I, _P],
     "pdeip_seg_label": [_P, _I, _I, _I, _P],
+    # connected components (csrc/pdeip_ccl.hip)
+    "pdeip_bwlabel_dev": [_P, _P, _I, _I, _I, _P, _P, _P, _I],
+    "pdeip_bwlabel": [_P, _I, _I, _I, _P, _P, _P, _I],
+    "pdeip_largest_component_dev": [_P, _P, _I, _I, _I, _F, _F, _P, _P, _P],
+    "pdeip_largest_component": [_P, _I, _I, _I, _F, _F, _P, _P, _P],
+    # generateSeeds() and the dense driver (csrc/pdeip_segmentation.hip)
+    "pdeip_generate_seeds": [_P, _P, _I, _I, _I, ctypes.c_double, _P, _I, _I, _I, ctypes.c_double, ctypes.c_double, ctypes.c_ulonglong, _P, _P, _P,
+                             _P, _P, _P],
+    "pdeip_disp_segmentation": [_P, _I, _I, _P, _I, _P, _P, ctypes.c_ulonglong, _P, _P, _P, _P],
     # library state
     "pdeip_set_mode": [_I],
     "pdeip_get_mode": [],

@@ -5,13 +5,16 @@
 //     `iterations` competition iterations on one scale, resident          pdeip_seg_competition_level(_dev)
 //     the whole regionCompetition() over its scale pyramid                pdeip_region_competition
 //   the numbered segment map (DispSegmentation.m:190-198)                 pdeip_seg_label(_dev)
+//   generateSeeds() (DispSegmentation.m:203-443)                          pdeip_generate_seeds
+//   the dense driver (DispSegmentation.m:31-198)                          pdeip_disp_segmentation
 //
-// Kernels: csrc/pdeip_segmentation.hpp; the contract: include/pdeip.h.  The fit is pdeip_surface_fit_masked_dev, the terms and the
+// Kernels: csrc/pdeip_segmentation.hpp; the seed loop's host-side schedule: csrc/pdeip_seeds_plan.hpp; the contract: include/pdeip.h.  The fit is pdeip_surface_fit_masked_dev, the terms and the
 // step pdeip_cv_terms_dev / pdeip_cv_solver_dev.  pdeip_set_mode does not apply.
 //
 // Build (build.py): hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -c, one object per translation unit.
 #include "pdeip_ctx.hpp"
 #include "pdeip_segmentation.hpp"
+#include "pdeip_seeds_plan.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -405,5 +408,244 @@ extern "C" int pdeip_region_competition(const float *D, const float *PHI, int nr
     } else {
         HIPCHK(hipDeviceSynchronize());
     }
+    return PDEIP_OK;
+}
+
+// ---- generateSeeds() (DispSegmentation.m:203-443): seed after seed, each grown over the visits [1..K, K..1] -----------------------
+namespace {
+
+int check_seeds(const char *who, int nrows, int ncols, int order, double sigmaLim, const double *cset_vect, int n_cset, int iterations, int n_seeds,
+                double scl_factor, double pyr_scl)
+{
+    char buf[160];
+    const char *bad = seeds::check_args(buf, sizeof buf, nrows, ncols, order, sigmaLim, cset_vect, n_cset, iterations, n_seeds, scl_factor, pyr_scl);
+    return bad ? set_err(PDEIP_ERR_ARG, "%s: %s", who, bad) : PDEIP_OK;
+}
+
+} // namespace
+
+extern "C" int pdeip_generate_seeds(const float *D, const float *AA, int nrows, int ncols, int order, double sigmaLim, const double *cset_vect,
+                                    int n_cset, int iterations, int n_seeds, double scl_factor, double pyr_scl, unsigned long long seed,
+                                    unsigned long long *fit_counter, const pdeip_seeds_params *prm, pdeip_seeds_trace *trace, int *S_out,
+                                    float *PHI_out, float *surf_out)
+{
+    const char *who = "pdeip_generate_seeds";
+    tls.err[0] = '\0'; // a call that succeeds leaves pdeip_last_error() empty
+    NONNULL(who, D); NONNULL(who, S_out); NONNULL(who, PHI_out); NONNULL(who, surf_out);
+    RC(check_seeds(who, nrows, ncols, order, sigmaLim, cset_vect, n_cset, iterations, n_seeds, scl_factor, pyr_scl));
+    const seeds::Prm p = seeds::resolve(prm ? &prm->dist_cap : nullptr, prm ? &prm->nan_fill : nullptr, prm ? &prm->mincov_gate : nullptr);
+    const std::vector<seeds::Size> sz = seeds::scale_sizes(nrows, ncols, scl_factor, pyr_scl);
+    const int K = (int)sz.size(), ncoef = order == 1 ? 3 : 6;
+    const bool fill = !std::isnan(p.nan_fill);
+    RC(use_device());
+    hipStream_t s = nullptr;
+    const size_t n0 = (size_t)nrows * ncols, nP = pad4(n0);
+    size_t nD = 0;
+    for (auto &q : sz) nD += pad4((size_t)q.r * q.c);
+    // workspace: cov (a double) first, then the count, the model, the pyramids of D, of D without NaNs and of AA, six planes
+    float *ws = nullptr;
+    RC(ws_get(WS_SEEDS, (4 + 4 + 8 + (fill ? 3 : 2) * nD + 6 * nP) * sizeof(float), &ws));
+    double *cov = reinterpret_cast<double *>(ws);
+    int *cnt = reinterpret_cast<int *>(ws + 4);
+    float *M = ws + 8, *at = M + 8;
+    std::vector<float *> Dp((size_t)K), Df((size_t)K), Ap((size_t)K);
+    for (int pass = 0; pass < (fill ? 3 : 2); pass++)
+        for (int k = 0; k < K; k++) {
+            (pass == 0 ? Dp : pass == 1 ? Ap : Df)[(size_t)k] = at;
+            at += pad4((size_t)sz[k].r * sz[k].c);
+        }
+    float *cur = at, *nxt = cur + nP, *DATA = nxt + nP, *DH = DATA + nP, *GRAD = DH + nP, *DIST = GRAD + nP;
+    int *host_cnt = nullptr;
+    RC(pinned_sizes(4, &host_cnt)); // the count in word 0, the variance of v = K (a double) in words 2-3 of the level call's pinned block
+    double *host_cov = reinterpret_cast<double *>(host_cnt + 2);
+    double *psum = nullptr;
+    int *pcnt = nullptr;
+
+    HIPCHK(hipMemcpy(Dp[0], D, n0 * sizeof(float), hipMemcpyHostToDevice));
+    {
+        std::vector<float> a(n0, 1.0f); // AA{1}: all ones, or the caller's with its NaNs counted as 0
+        if (AA)
+            for (size_t i = 0; i < n0; i++) a[i] = AA[i] != AA[i] ? 0.0f : AA[i];
+        HIPCHK(hipMemcpy(Ap[0], a.data(), n0 * sizeof(float), hipMemcpyHostToDevice));
+    }
+    for (int k = 1; k < K; k++) RC(pdeip_pyr_resize_dev(s, Dp[k - 1], sz[k - 1].r, sz[k - 1].c, 1, sz[k].r, sz[k].c, 1, Dp[k]));
+    for (int k = 0; k < K; k++) {
+        if (!fill) { Df[(size_t)k] = Dp[(size_t)k]; continue; }
+        const int npix = sz[k].r * sz[k].c;
+        hipLaunchKernelGGL(k_seg_nanfill, dim3((unsigned)tiles_of(npix)), dim3(SG_BLOCK), 0, s, Dp[k], npix, p.nan_fill, Df[k]);
+        HIPCHK(hipGetLastError());
+    }
+
+    if (trace) trace->n_counts = trace->n_largest = 0;
+    const size_t nK = (size_t)sz[K - 1].r * sz[K - 1].c;
+    double gamma = seeds::GAMMA0;
+    unsigned long long fit = fit_counter ? *fit_counter : 0ull;
+    int S = 0;
+    for (int sd = 0; sd < n_seeds; sd++) {
+        for (int k = 1; k < K; k++) RC(pdeip_pyr_resize_dev(s, Ap[k - 1], sz[k - 1].r, sz[k - 1].c, 1, sz[k].r, sz[k].c, 1, Ap[k]));
+        double minCOV = sigmaLim;
+        hipLaunchKernelGGL(k_seeds_init, dim3((unsigned)tiles_of((int)n0)), dim3(SG_BLOCK), 0, s, nrows, ncols, cur);
+        HIPCHK(hipGetLastError());
+        bool empty = false;
+        for (int v = 0; v < 2 * K; v++) {
+            const int k = seeds::visit_scale(v, K), r = sz[k].r, c = sz[k].c, npix = r * c;
+            const dim3 grid((unsigned)tiles_of(npix)), blk(SG_BLOCK);
+            RC(stage_ws(npix, 1, &psum, &pcnt));
+            if (v == 0) hipLaunchKernelGGL(k_seeds_exclude, grid, blk, 0, s, Ap[k], npix, seeds::INCLUDE_ABOVE, -1.0f, cur);
+            bool have_model = false; // H1eq = [] (:279)
+            if (v == K) { // once per seed only the biggest connected element survives (:282-298)
+                RC(pdeip_largest_component_dev(s, cur, r, c, 8, 5.0f, -5.0f, cur, nullptr, nullptr));
+                if (trace && trace->largest) {
+                    HIPCHK(hipMemcpyAsync(trace->largest + (size_t)trace->n_largest * nK, cur, nK * sizeof(float), hipMemcpyDeviceToHost, s));
+                    trace->n_largest++;
+                }
+            }
+            const float nu = seeds::nu_of(gamma, r, c);
+            for (int it = 1; it <= iterations; it++) {
+                // the count, read back once: it decides whether the seed goes on
+                RC(launch_sizes(s, cur, npix, 1, pcnt, cnt));
+                HIPCHK(hipMemcpyAsync(host_cnt, cnt, sizeof(int), hipMemcpyDeviceToHost, s));
+                HIPCHK(hipStreamSynchronize(s));
+                if (trace && trace->counts && trace->n_counts < trace->counts_cap) trace->counts[trace->n_counts] = *host_cnt;
+                if (trace) trace->n_counts++;
+                if (*host_cnt < seeds::EMPTY_BELOW) {
+                    empty = true;
+                    break;
+                }
+                RC(pdeip_surface_fit_masked_dev(s, cur, Df[k], r, c, order, have_model ? M : nullptr, seeds::ERR_THR,
+                                                (float)seeds::rcons(cset_vect, n_cset, it, v), seeds::riter(it, v), nullptr, seed + 65536ull * fit, M,
+                                                DIST, nullptr));
+                fit++;
+                have_model = true;
+                RC(launch_variance(s, cur, DIST, npix, 1, minCOV, p.dist_cap, psum, pcnt, cov, nullptr));
+                RC(pdeip_cv_terms_dev(s, cur, r, c, 1, 1.0f, 1.0f, std::numeric_limits<float>::quiet_NaN(), DH, GRAD));
+                RC(launch_data(s, DIST, cur, DH, cov, npix, 1, PDEIP_SEG_INVERSE, DATA, nullptr));
+                hipLaunchKernelGGL(k_seeds_exclude, grid, blk, 0, s, Ap[k], npix, seeds::INCLUDE_ABOVE, -2.0f, DATA);
+                HIPCHK(hipGetLastError());
+                RC(pdeip_cv_solver_dev(s, cur, DATA, DH, GRAD, r, c, 1, 1.0f, nu, nxt));
+                std::swap(cur, nxt);
+            }
+            if (empty) {
+                gamma *= seeds::GAMMA_SHRINK; // persists over the remaining seeds (:402-405)
+                break;
+            }
+            if (v == K && iterations > 0) { // minCOV = the unfloored variance of the last iteration: its H1 (nxt) and distD (:408-412)
+                RC(launch_variance(s, nxt, DIST, npix, 1, -std::numeric_limits<double>::infinity(), p.dist_cap, psum, pcnt, cov, nullptr));
+                HIPCHK(hipMemcpyAsync(host_cov, cov, sizeof(double), hipMemcpyDeviceToHost, s));
+                HIPCHK(hipStreamSynchronize(s));
+                if (*host_cov > p.mincov_gate) minCOV = *host_cov; // a NaN never exceeds the gate
+            }
+            if (v + 1 < 2 * K) {
+                const int kn = seeds::visit_scale(v + 1, K);
+                RC(pdeip_pyr_resize_dev(s, cur, r, c, 1, sz[kn].r, sz[kn].c, 1, nxt));
+                std::swap(cur, nxt);
+            }
+        }
+        if (empty) continue;
+        HIPCHK(hipMemcpyAsync(PHI_out + (size_t)S * n0, cur, n0 * sizeof(float), hipMemcpyDeviceToHost, s));
+        if (iterations > 0) HIPCHK(hipMemcpyAsync(surf_out + (size_t)S * ncoef, M, (size_t)ncoef * sizeof(float), hipMemcpyDeviceToHost, s));
+        else std::fill(surf_out + (size_t)S * ncoef, surf_out + (size_t)(S + 1) * ncoef, std::numeric_limits<float>::quiet_NaN()); // no fit: no model
+        S++;
+        hipLaunchKernelGGL(k_seeds_allowed, dim3((unsigned)tiles_of((int)n0)), dim3(SG_BLOCK), 0, s, cur, (int)n0, Ap[0]);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    if (fit_counter) *fit_counter = fit;
+    *S_out = S;
+    return PDEIP_OK;
+}
+
+// ---- [PHI SEG SParam] = DispSegmentation(Din, param) (DispSegmentation.m:31-198) ------------------------------------------------
+extern "C" int pdeip_disp_segmentation(const float *Din, int nrows, int ncols, const float *PHIin, int S_in, const float *AA,
+                                       const pdeip_dispseg_params *prm, unsigned long long seed, int *S_out, float *PHI_out, int *SEG_out,
+                                       float *surf_out)
+{
+    const char *who = "pdeip_disp_segmentation";
+    tls.err[0] = '\0';
+    NONNULL(who, Din); NONNULL(who, S_out); NONNULL(who, PHI_out); NONNULL(who, SEG_out); NONNULL(who, surf_out);
+    seeds::DriverPrm p = seeds::driver_defaults();
+    if (prm) {
+        if (!std::isnan(prm->srem_thr)) p.srem_thr = prm->srem_thr;
+        if (!std::isnan(prm->scl_factor)) p.scl_factor = prm->scl_factor;
+        if (!std::isnan(prm->gen_scl)) p.gen_scl = prm->gen_scl;
+        if (!std::isnan(prm->rc_scl)) p.rc_scl = prm->rc_scl;
+        if (!std::isnan(prm->ransac_min_cset)) p.ransac_min_cset = prm->ransac_min_cset;
+        if (!std::isnan(prm->ransac_max_cset)) p.ransac_max_cset = prm->ransac_max_cset;
+        if (prm->polyorder != 0) p.polyorder = prm->polyorder;
+        if (prm->seeds != 0) p.seeds = prm->seeds;
+        if (prm->ransac_cset_cycles != 0) p.ransac_cset_cycles = prm->ransac_cset_cycles;
+    }
+    {
+        char buf[160];
+        const char *bad = seeds::check_driver(buf, sizeof buf, p);
+        if (bad) return set_err(PDEIP_ERR_ARG, "%s: %s", who, bad);
+    }
+    if (PHIin && S_in < 1) return set_err(PDEIP_ERR_ARG, "%s: PHIin given with S_in = %d", who, S_in);
+    const std::vector<double> cset = seeds::cset_vector(p.ransac_min_cset, p.ransac_max_cset, p.ransac_cset_cycles);
+    const int cap = PHIin ? S_in + 1 : 2 * p.seeds;
+    RC(check_seeds(who, nrows, ncols, p.polyorder, 0.7, cset.data(), (int)cset.size(), 20, std::max(cap, 1), p.scl_factor, p.gen_scl));
+    const SegPrm dense = seg_resolve(nullptr);
+    RC(check_level(who, nrows, ncols, cap, p.polyorder, PDEIP_SEG_INVERSE, 1.0, (float)p.ransac_max_cset, 20, p.srem_thr, dense));
+
+    const size_t n0 = (size_t)nrows * ncols;
+    const int ncoef = p.polyorder == 1 ? 3 : 6;
+    std::vector<float> Dz(Din, Din + n0), A(n0), P((size_t)cap * n0), Q((size_t)cap * n0);
+    std::vector<int> kept((size_t)cap);
+    for (auto &d : Dz)
+        if (d != d) d = 0.0f; // we don't like NaNs (:61)
+    int live = 0, stage = 0;
+    *S_out = 0;
+    auto compete = [&](double sigmaLim, int iterations) -> int { // P -> P
+        int out = 0;
+        RC(pdeip_region_competition(Dz.data(), P.data(), nrows, ncols, live, p.polyorder, PDEIP_SEG_INVERSE, sigmaLim, (float)p.ransac_max_cset,
+                                    iterations, p.srem_thr, p.scl_factor, p.rc_scl, seeds::stage_seed(seed, stage++), nullptr, &out, Q.data(),
+                                    surf_out, kept.data()));
+        live = out;
+        std::swap(P, Q);
+        return PDEIP_OK;
+    };
+    auto more_seeds = [&](double sigmaLim, const float *allowed, int n, double pyr_scl) -> int { // appends to P
+        int out = 0;
+        RC(pdeip_generate_seeds(Dz.data(), allowed, nrows, ncols, p.polyorder, sigmaLim, cset.data(), (int)cset.size(), 20, n, p.scl_factor, pyr_scl,
+                                seeds::stage_seed(seed, stage++), nullptr, nullptr, nullptr, &out, P.data() + (size_t)live * n0,
+                                surf_out + (size_t)live * ncoef));
+        live += out;
+        return PDEIP_OK;
+    };
+    auto uncovered = [&]() { // sum(PHI > 0, 3) == 0
+        for (size_t i = 0; i < n0; i++) {
+            bool any = false;
+            for (int k = 0; k < live && !any; k++) any = P[(size_t)k * n0 + i] > 0.0f;
+            A[i] = any ? 0.0f : 1.0f;
+        }
+    };
+    if (!PHIin) {
+        const float *allowed = nullptr; // param.AA == 1; an empty AA allows everything
+        if (AA) {
+            for (size_t i = 0; i < n0; i++) A[i] = AA[i] == 1.0f ? 1.0f : 0.0f;
+            allowed = A.data();
+        }
+        RC(more_seeds(0.7, allowed, p.seeds, p.gen_scl));
+        if (live == 0) return PDEIP_OK;
+        if (p.seeds != 1) {
+            RC(compete(1.5, 30));
+            if (live == 0) return PDEIP_OK;
+            uncovered();
+            RC(more_seeds(1.2, A.data(), p.seeds, p.rc_scl));
+            RC(compete(1.5, 20));
+        }
+    } else {
+        std::copy(PHIin, PHIin + (size_t)S_in * n0, P.begin());
+        live = S_in;
+        RC(compete(1.0, 20));
+        if (live == 0) return PDEIP_OK;
+        uncovered();
+        RC(more_seeds(1.2, A.data(), 1, p.rc_scl));
+        RC(compete(2.0, 20));
+    }
+    if (live == 0) return PDEIP_OK;
+    std::copy(P.begin(), P.begin() + (size_t)live * n0, PHI_out);
+    RC(pdeip_seg_label(PHI_out, nrows, ncols, live, SEG_out));
+    *S_out = live;
     return PDEIP_OK;
 }

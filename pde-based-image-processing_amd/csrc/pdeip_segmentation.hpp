@@ -12,6 +12,7 @@
 //   k_seg_data                             likelihood, competitor and log-odds per pixel, O(S): two passes over the segments
 //   k_seg_label                            the numbered map
 //   k_seg_nanfill                          D with its NaNs replaced (the sparse driver's DinNoNaN)
+//   k_seeds_init / _exclude / _allowed     generateSeeds(): the initial grid of seeds, plane(~include) = value, the allowed area
 // A tile is SG_BLOCK pixels in memory (column-major) order; segments are on blockIdx.y.
 #pragma once
 #include "pdeip_ctx.hpp"
@@ -208,6 +209,33 @@ __global__ void __launch_bounds__(SG_BLOCK) k_seg_nanfill(const float *__restric
     if (p >= npix) return;
     const float d = D[p];
     out[p] = d != d ? fill : d;
+}
+
+// ---- generateSeeds(): its per-pixel glue (DispSegmentation.m:238-239, 276-277, 374, 426) ----
+// PHIinitial: -1, +1 at the 0-based rows 1, 6, 11, .. <= nrows - 2 and columns 1, 6, .. <= ncols - 2.
+__global__ void __launch_bounds__(SG_BLOCK) k_seeds_init(int nrows, int ncols, float *__restrict__ PHI)
+{
+    const int p = blockIdx.x * SG_BLOCK + threadIdx.x;
+    if (p >= nrows * ncols) return;
+    const int i = p % nrows, j = p / nrows;
+    const bool on = i >= 1 && i <= nrows - 2 && j >= 1 && j <= ncols - 2 && (i - 1) % 5 == 0 && (j - 1) % 5 == 0;
+    PHI[p] = on ? 1.0f : -1.0f;
+}
+
+// plane(~(AA > thr)) = value; a NaN AA is outside.
+__global__ void __launch_bounds__(SG_BLOCK) k_seeds_exclude(const float *__restrict__ AA, int npix, float thr, float value, float *__restrict__ plane)
+{
+    const int p = blockIdx.x * SG_BLOCK + threadIdx.x;
+    if (p >= npix) return;
+    if (!(AA[p] > thr)) plane[p] = value;
+}
+
+// AA = (PHI < 0) && (AA != 0), as 1 / 0.
+__global__ void __launch_bounds__(SG_BLOCK) k_seeds_allowed(const float *__restrict__ PHI, int npix, float *__restrict__ AA)
+{
+    const int p = blockIdx.x * SG_BLOCK + threadIdx.x;
+    if (p >= npix) return;
+    AA[p] = (PHI[p] < 0.0f && AA[p] != 0.0f) ? 1.0f : 0.0f;
 }
 
 } // namespace seg

@@ -686,3 +686,46 @@ def seg_label(PHI, SEG_out=None):
     _chk_typed(SEG_out, torch.int32, nrows * ncols, "seg_label: SEG_out")
     capi.call("pdeip_seg_label_dev", _stream(), PHI.data_ptr(), nrows, ncols, S, SEG_out.data_ptr())
     return SEG_out
+
+
+def bwlabel(A, conn=8, L_out=None, num_out=None, areas_out=None):
+    """[L, num] = bwlabel(A > 0, conn) with MATLAB's numbering (pdeip_bwlabel_dev): A float32 [ncols, nrows]; L_out int32 like A,
+    num_out int32 [1], areas_out int32 [cap] or None (areas_out[l-1] = pixels of component l).  Returns (L_out, num_out, areas_out)
+    as tensors; nothing is read back."""
+    _chk(A)
+    if A.dim() != 2:
+        raise capi.PdeipError(capi.PDEIP_ERR_ARG, "bwlabel: A must be one plane [ncols, nrows]")
+    nrows, ncols, _ = _dims(A)
+    if L_out is None:
+        L_out = torch.empty(A.shape, dtype=torch.int32, device=A.device)
+    if num_out is None:
+        num_out = torch.empty(1, dtype=torch.int32, device=A.device)
+    _chk_typed(L_out, torch.int32, nrows * ncols, "bwlabel: L_out")
+    _chk_typed(num_out, torch.int32, 1, "bwlabel: num_out")
+    cap = 0
+    if areas_out is not None:
+        cap = int(areas_out.numel())
+        _chk_typed(areas_out, torch.int32, cap, "bwlabel: areas_out")
+    capi.call("pdeip_bwlabel_dev", _stream(), A.data_ptr(), nrows, ncols, int(conn), L_out.data_ptr(), num_out.data_ptr(),
+              areas_out.data_ptr() if cap else None, cap)
+    return L_out, num_out, areas_out
+
+
+def largest_component(A, conn=8, hi=1.0, lo=0.0, out=None, num_out=None, area_out=None):
+    """out = lo everywhere, hi on the largest component of A > 0 (the lowest label on a tie; pdeip_largest_component_dev).  out
+    float32 like A (A itself is allowed); num_out / area_out int32 [1] or None.  Returns out."""
+    _chk(A)
+    if A.dim() != 2:
+        raise capi.PdeipError(capi.PDEIP_ERR_ARG, "largest_component: A must be one plane [ncols, nrows]")
+    nrows, ncols, _ = _dims(A)
+    if out is None:
+        out = torch.empty_like(A)
+    _chk(out)
+    if out.numel() != A.numel():
+        raise capi.PdeipError(capi.PDEIP_ERR_ARG, "largest_component: out must have A's shape")
+    for t, what in ((num_out, "num_out"), (area_out, "area_out")):
+        if t is not None:
+            _chk_typed(t, torch.int32, 1, "largest_component: " + what)
+    capi.call("pdeip_largest_component_dev", _stream(), A.data_ptr(), nrows, ncols, int(conn), float(hi), float(lo), out.data_ptr(),
+              num_out.data_ptr() if num_out is not None else None, area_out.data_ptr() if area_out is not None else None)
+    return out

@@ -25,6 +25,7 @@ MATLAB session the toolbox runs in; the `capi_*` functions at the end of this fi
 `graph=True` (the llin flow drivers and the FAS driver, parallel orderings): the run's launches are captured into a HIP graph
 on the first call for a frame size and replayed afterwards (graphs.py) -- same kernels and bits, no per-launch host work.
 """
+import ctypes
 import math
 
 import numpy as np
@@ -276,8 +277,6 @@ _TERM = {"NONE": 0, "RGB": 1, "GRAD": 2, "GRADMAG": 3}
 
 
 def _c_params(param):
-    import ctypes
-
     class P(ctypes.Structure):
         _fields_ = [(k, ctypes.c_double) for k in ("alpha", "omega", "gammaS", "b1", "b2", "scl_factor")] + \
                    [(k, ctypes.c_int) for k in ("firstLoop", "secondLoop", "iter", "solver", "scales")]
@@ -298,7 +297,6 @@ def _f_double(a):
 
 def capi_FlowEminND_llin_2D_v10(Iin, channels, fstTerm="rgb", sndTerm="none", mode=capi.MODE_EXACT_ORDER, Us=None, Vs=None, **param):
     """pdeip_flow_nd_llin on MATLAB-shaped numpy arrays: the C++ twin of FlowEminND_llin_2D_v10 above, same bits."""
-    import ctypes
     I = _f_single(Iin)
     rows, cols = I.shape[:2]
     U, V = np.zeros((rows, cols), np.float32, order="F"), np.zeros((rows, cols), np.float32, order="F")
@@ -316,7 +314,6 @@ def capi_FlowEminND_llin_2D_v10(Iin, channels, fstTerm="rgb", sndTerm="none", mo
 
 def capi_DispEminND_llin_2D(Il, Ir, fstTerm="rgb", sndTerm="none", mode=capi.MODE_EXACT_ORDER, Us=None, **param):
     """pdeip_disp_nd_llin on MATLAB-shaped numpy arrays."""
-    import ctypes
     L, R = _f_single(Il), _f_single(Ir)
     rows, cols, C = L.shape
     U = np.zeros((rows, cols), np.float32, order="F")
@@ -333,8 +330,6 @@ def capi_DispEminND_llin_2D(Il, Ir, fstTerm="rgb", sndTerm="none", mode=capi.MOD
 
 
 def _c_tv_params(param):
-    import ctypes
-
     class P(ctypes.Structure):
         _fields_ = [(k, ctypes.c_double) for k in ("alpha", "omega", "scl", "scl_factor")] + [(k, ctypes.c_int) for k in ("outer_iter", "inner_iter", "solver")]
     s = P()
@@ -344,7 +339,6 @@ def _c_tv_params(param):
 
 
 def _capi_tv(entry, I_in, mode, param):
-    import ctypes
     I = _f_single(I_in)
     rows, cols, F = I.shape
     out = np.zeros((rows, cols, F), np.float32, order="F")
@@ -370,7 +364,6 @@ def capi_TVdenoise4(I_in, mode=capi.MODE_EXACT_ORDER, **param):
 
 def capi_FlowEminHS_elin_2D_v10(Iin, channels, mode=capi.MODE_EXACT_ORDER, **param):
     """pdeip_flow_hs_elin: the C++ twin of FlowEminHS_elin_2D_v10 above, same bits."""
-    import ctypes
     I = _f_single(Iin)
     rows, cols = I.shape[:2]
     U, V = np.zeros((rows, cols), np.float32, order="F"), np.zeros((rows, cols), np.float32, order="F")
@@ -386,8 +379,6 @@ def capi_FlowEminHS_elin_2D_v10(Iin, channels, mode=capi.MODE_EXACT_ORDER, **par
 
 def capi_DispEminND_llin_sym_2D(Il, Ir, mode=capi.MODE_EXACT_ORDER, **param):
     """pdeip_disp_nd_llin_sym: the C++ twin of DispEminND_llin_sym_2D above, same bits; -> U [nrows, ncols, 2]."""
-    import ctypes
-
     class P(ctypes.Structure):
         _fields_ = [(k, ctypes.c_double) for k in ("alpha", "beta", "omega", "b1", "b2", "scl_factor")] + \
                    [(k, ctypes.c_int) for k in ("firstLoop", "secondLoop", "iter", "solver")]
@@ -408,7 +399,6 @@ def capi_DispEminND_llin_sym_2D(Il, Ir, mode=capi.MODE_EXACT_ORDER, **param):
 
 def capi_FlowEminAD_llin_2D_v10(Iin, channels, fstTerm="rgb", sndTerm="none", mode=capi.MODE_EXACT_ORDER, Us=None, Vs=None, quantile=0.0, diffusion="image", **param):
     """pdeip_flow_ad_llin: the C++ twin of FlowEminAD_llin_2D_v10 above, same bits."""
-    import ctypes
     I = _f_single(Iin)
     rows, cols = I.shape[:2]
     U, V = np.zeros((rows, cols), np.float32, order="F"), np.zeros((rows, cols), np.float32, order="F")
@@ -427,8 +417,6 @@ def capi_FlowEminAD_llin_2D_v10(Iin, channels, fstTerm="rgb", sndTerm="none", mo
 
 def capi_FlowEminNDFASFMG_elin_2D_v10(Iin, channels, mode=capi.MODE_EXACT_ORDER, **param):
     """pdeip_flow_fas_fmg_elin: the C++ twin of FlowEminNDFASFMG_elin_2D_v10 above, same bits."""
-    import ctypes
-
     class P(ctypes.Structure):
         _fields_ = [(k, ctypes.c_double) for k in ("alpha", "omega", "b1", "b2", "scl_factor")] + \
                    [(k, ctypes.c_int) for k in ("firstLoop", "iter", "solver", "cycle_index", "scales")]
@@ -455,8 +443,6 @@ _GAC_KEYS = {"tau": "tau", "c": "c", "lambda": "lambda_", "lambda_": "lambda_", 
 
 
 def _gac(Iin, PHIin, model, param):
-    import ctypes
-
     prm = _GacParams(*([float("nan")] * 5))  # NaN: the driver's default
     for k, v in param.items():
         if k not in _GAC_KEYS or (model == 1 and k == "c"):
@@ -498,8 +484,6 @@ def Diffusion4_v10(I_in, as_single=False, **param):
     """Iout = Diffusion4_v10(I_in, ...) (matlab/diffusion/Diffusion4_v10.m): nonlinear (lagged-diffusivity) diffusion, the whole
     run in one pdeip_diffusion4 call.  I_in [rows, cols(, C)] in any numeric type, taken as single(I_in); param: alpha (25),
     outer_iter (5), as the driver names them.  Returns uint8(Iout) by MATLAB's rule, or the single Iout with as_single=True."""
-    import ctypes
-
     for k in param:
         if k not in ("alpha", "outer_iter"):
             raise TypeError("Diffusion4_v10: unknown parameter %r" % k)
@@ -548,8 +532,6 @@ def regionCompetition(D, PHI, polyorder, sigmaLim, ransac_cset, iterations, srem
     call: the D pyramid (scl_factor, rc_scl as the drivers' param struct names them), the visits down and up, every iteration
     resident.  param overrides single constants (c0, c1, dh_floor, err_thr, gamma_coef, dist_cap, nan_fill).  Returns (PHI [rows,
     cols, S_out], SParam [ncoef, S_out], kept: the 0-based input index of each surviving segment)."""
-    import ctypes
-
     prm = dev.SegParams.make(sparse=sparse, **param)
     Dm = np.asfortranarray(np.asarray(D, dtype=np.float32))
     P = _planes3(PHI)
@@ -577,3 +559,125 @@ def segments_numbered(PHI):
     out = np.zeros((rows, cols), np.int32, order="F")
     capi.call("pdeip_seg_label", P.ctypes.data, rows, cols, S, out.ctypes.data)
     return out
+
+
+def bwlabel(BW, conn=8):
+    """[L, num] = bwlabel(BW, conn) with MATLAB's numbering (components 1..num in the order of their first pixel in column-major
+    order, 0 for background), one pdeip_bwlabel call.  BW [rows, cols]: a logical array, or numbers of which the positive ones are
+    foreground (the drivers call bwlabel(PHI > 0)).  Returns (L float64 [rows, cols] as MATLAB's is, num)."""
+    B = np.asarray(BW)
+    if B.ndim != 2:
+        raise ValueError("bwlabel: BW must be two-dimensional (got %s)" % (B.shape,))
+    A = np.asfortranarray((B > 0).astype(np.float32))
+    rows, cols = A.shape
+    L = np.zeros((rows, cols), np.int32, order="F")
+    num = ctypes.c_int(0)
+    capi.call("pdeip_bwlabel", A.ctypes.data, rows, cols, int(conn), L.ctypes.data, ctypes.addressof(num), None, 0)
+    return np.asfortranarray(L.astype(np.float64)), num.value
+
+
+class _SeedsParams(ctypes.Structure):
+    """pdeip_seeds_params: NaN keeps the dense driver's value."""
+    _fields_ = [(k, ctypes.c_double) for k in ("dist_cap", "nan_fill", "mincov_gate")]
+
+
+class _SeedsTrace(ctypes.Structure):
+    """pdeip_seeds_trace."""
+    _fields_ = [("counts", ctypes.c_void_p), ("counts_cap", ctypes.c_int), ("n_counts", ctypes.c_int), ("largest", ctypes.c_void_p),
+                ("n_largest", ctypes.c_int)]
+
+
+class _DispSegParams(ctypes.Structure):
+    """pdeip_dispseg_params: NaN / 0 keeps the .m's default."""
+    _fields_ = [(k, ctypes.c_double) for k in ("srem_thr", "scl_factor", "gen_scl", "rc_scl", "ransac_min_cset", "ransac_max_cset")] + \
+               [(k, ctypes.c_int) for k in ("polyorder", "seeds", "ransac_cset_cycles")]
+
+
+def generateSeeds(D, polyorder, sigmaLim, cset_vect, iterations, AA=None, seeds=15, sparse=False, seed=0, scl_factor=0.7, pyr_scl=0.2,
+                  fit_counter=0, trace=None, **param):
+    """[PHIout SParam] = generateSeeds(D, pyramid, polyorder, sigmaLim, ransac_cset_vect, iterations, srem_thr, AAin, seeds) of
+    matlab/segmentation/DispSegmentation.m (sparse=True: DispSegmentationSparse.m's constants dist_cap 100, nan_fill 1000,
+    mincov_gate 0.5) in one pdeip_generate_seeds call; the pyramid is given by scl_factor and pyr_scl (the drivers' gen_scl or
+    rc_scl).  param overrides single constants.  trace: a dict that receives counts (every count read back), largest (the v = K
+    largest-component planes [rK, cK, n]) and fit_counter.  Returns (PHI [rows, cols, S_out], SParam [ncoef, S_out])."""
+    vals = dict(dist_cap=100.0, nan_fill=1000.0, mincov_gate=0.5) if sparse else {}
+    for k, v in param.items():
+        if k not in dict(_SeedsParams._fields_):
+            raise TypeError("unknown generateSeeds parameter %r" % k)
+        vals[k] = float(v)
+    prm = _SeedsParams(*[vals.get(k, float("nan")) for k, _ in _SeedsParams._fields_])
+    Dm = np.asfortranarray(np.asarray(D, dtype=np.float32))
+    if Dm.ndim != 2:
+        raise ValueError("generateSeeds: D must be two-dimensional (got %s)" % (Dm.shape,))
+    rows, cols = Dm.shape
+    Am = None
+    if AA is not None:
+        Am = np.asfortranarray(np.asarray(AA, dtype=np.float32))
+        if Am.shape != Dm.shape:
+            raise ValueError("generateSeeds: AA is %s but D is %s" % (Am.shape, Dm.shape))
+    cs = np.ascontiguousarray(np.asarray(cset_vect, dtype=np.float64).reshape(-1))
+    seeds, iterations = int(seeds), int(iterations)
+    ncoef = 6 if polyorder == 2 else 3
+    n = max(seeds, 1)
+    out = np.zeros((rows, cols, n), np.float32, order="F")
+    surf = np.zeros((ncoef, n), np.float32, order="F")
+    s_out = ctypes.c_int(0)
+    fit = ctypes.c_ulonglong(int(fit_counter) & ((1 << 64) - 1))
+    tr, counts, largest = None, None, None
+    if trace is not None:
+        cap = n * (max(iterations, 0) + 1) * 64
+        counts = np.zeros(cap, np.int32)
+        largest = np.zeros(rows * cols * n, np.float32)  # no scale is larger than the first
+        tr = _SeedsTrace(counts.ctypes.data, cap, 0, largest.ctypes.data, 0)
+    capi.call("pdeip_generate_seeds", Dm.ctypes.data, None if Am is None else Am.ctypes.data, rows, cols, int(polyorder), float(sigmaLim),
+              cs.ctypes.data, int(cs.size), iterations, seeds, float(scl_factor), float(pyr_scl),
+              ctypes.c_ulonglong(int(seed) & ((1 << 64) - 1)), ctypes.addressof(fit), ctypes.addressof(prm),
+              None if tr is None else ctypes.addressof(tr), ctypes.addressof(s_out), out.ctypes.data, surf.ctypes.data)
+    if trace is not None:
+        trace["counts"] = [int(c) for c in counts[:min(tr.n_counts, tr.counts_cap)]]
+        trace["n_counts"] = tr.n_counts
+        trace["largest"] = largest[:0] if tr.n_largest == 0 else largest
+        trace["n_largest"] = tr.n_largest
+        trace["fit_counter"] = int(fit.value)
+    k = s_out.value
+    return np.asfortranarray(out[:, :, :k]), np.asfortranarray(surf[:, :k])
+
+
+def DispSegmentation(Din, seed=0, PHI=None, AA=None, **param):
+    """[PHI SEG SParam] = DispSegmentation(Din, param) of matlab/segmentation/DispSegmentation.m in one pdeip_disp_segmentation
+    call.  param: the .m's fields srem_thr, polyorder, seeds, scl_factor, gen_scl, rc_scl, ransac_min_cset, ransac_max_cset,
+    ransac_cset_cycles (defaults as there); PHI (param.PHI) and AA (param.AA) as keywords.  Returns (PHI [rows, cols, S], SEG int32
+    [rows, cols], SParam [ncoef, S]); with no segment left: S = 0 and SEG all zero."""
+    names = dict(_DispSegParams._fields_)
+    for k in param:
+        if k not in names:
+            raise TypeError("unknown DispSegmentation parameter %r" % k)
+    prm = _DispSegParams(*[(float(param.get(k, float("nan"))) if t is ctypes.c_double else int(param.get(k, 0))) for k, t in _DispSegParams._fields_])
+    Dm = np.asfortranarray(np.asarray(Din, dtype=np.float32))
+    if Dm.ndim != 2:
+        raise ValueError("DispSegmentation: Din must be two-dimensional (got %s)" % (Dm.shape,))
+    rows, cols = Dm.shape
+    Pm, S_in = None, 0
+    if PHI is not None:
+        Pm = _planes3(PHI)
+        S_in = Pm.shape[2]
+        if Pm.shape[:2] != Dm.shape:
+            raise ValueError("DispSegmentation: PHI is %s but Din is %s" % (Pm.shape, Dm.shape))
+    Am = None
+    if AA is not None:
+        Am = np.asfortranarray(np.asarray(AA, dtype=np.float32))
+        if Am.shape != Dm.shape:
+            raise ValueError("DispSegmentation: AA is %s but Din is %s" % (Am.shape, Dm.shape))
+    polyorder = int(param.get("polyorder", 0)) or 1  # 0 keeps the .m's default, as in the C call
+    n_seeds = int(param.get("seeds", 0)) or 15
+    cap = max(S_in + 1 if Pm is not None else 2 * n_seeds, 1)
+    ncoef = 6 if polyorder == 2 else 3
+    out = np.zeros((rows, cols, cap), np.float32, order="F")
+    surf = np.zeros((ncoef, cap), np.float32, order="F")
+    SEG = np.zeros((rows, cols), np.int32, order="F")
+    s_out = ctypes.c_int(0)
+    capi.call("pdeip_disp_segmentation", Dm.ctypes.data, rows, cols, None if Pm is None else Pm.ctypes.data, S_in,
+              None if Am is None else Am.ctypes.data, ctypes.addressof(prm), ctypes.c_ulonglong(int(seed) & ((1 << 64) - 1)),
+              ctypes.addressof(s_out), out.ctypes.data, SEG.ctypes.data, surf.ctypes.data)
+    k = s_out.value
+    return np.asfortranarray(out[:, :, :k]), SEG, np.asfortranarray(surf[:, :k])
