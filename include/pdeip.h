@@ -465,12 +465,17 @@ int pdeip_sym_assemble_dev(void *stream, const float *Idt, const float *Idx, con
                            float *CuG, float *DuG);
 
 /* TVdenoise4's work between two PDEsolver4 calls (matlab/denoising/TVdenoise4.m:84-98 with DiffWeights :116-156), all single:
- * the four weights (maximum over the frames, outer column/row zeroed) scaled by alpha, PsiData, TRACE, B; [.. x nframes] each. */
+ * the four weights (maximum over the frames, outer column/row zeroed) scaled by alpha, PsiData, TRACE, B; [.. x nframes] each.
+ * The maximum over the frames is MATLAB's max: NaN is skipped, the result is NaN only where every frame is NaN. */
 int pdeip_tv4_assemble_dev(void *stream, const float *Iout, const float *Iin, int nrows, int ncols, int nframes, float alpha,
                            float *TRACE, float *B, float *aW, float *aN, float *aE, float *aS);
 /* [W NW N NE E SE S SW] = ADdiffWeights(D, quantile) of the anisotropic flow driver (matlab/optical_flow/
  * FlowEminAD_llin_2D_v10.m:416-487): Alvarez derivative in double, strongest frame per pixel, lambda = the quantile of the
- * non-zero squared gradient norms, tensor weights with circshift wrap-around; returned as single (the solver's arguments). */
+ * non-zero squared gradient norms, tensor weights with circshift wrap-around; returned as single (the solver's arguments).
+ * NaN in the frame maximum follows MATLAB's max: a frame whose squared norm is NaN is skipped, the first of the maximal numeric
+ * frames wins, and a pixel whose norm is NaN in every frame (or in the only one) takes frame 1, i.e. keeps NaN derivatives and a
+ * NaN norm.  In the selection of lambda a NaN norm is a non-zero one and the largest value (sort places NaN last): it moves
+ * the rank but becomes lambda only if the rank reaches it.  The same holds for pdeip_tv_assemble_dev. */
 int pdeip_ad_weights_dev(void *stream, const float *D, int nrows, int ncols, int nframes, double quantile, float *wW, float *wNW,
                          float *wN, float *wNE, float *wE, float *wSE, float *wS, float *wSW);
 
@@ -512,7 +517,11 @@ int pdeip_fas_upscale_dev(void *stream, const float *in, int nrows, int ncols, f
 int pdeip_tv_assemble_dev(void *stream, const float *Iout, const float *Iin, int nrows, int ncols, int nframes,
                           float alpha, float *TRACE, float *B, float *aW, float *aNW, float *aN, float *aNE,
                           float *aE, float *aSE, float *aS, float *aSW);
-/* out = medfilt2(A + B, [3 3], 'symmetric') (:352); B may be NULL (out = medfilt2(A)); out must not alias A or B */
+/* out = medfilt2(A + B, [3 3], 'symmetric') (:352); B may be NULL (out = medfilt2(A)); out must not alias A or B.
+ * Our definition where medfilt2's is not documented: the 5th of the nine window values (the edge pixel mirrored) in ascending
+ * order with NaN as the LARGEST value, above +Inf, as sort places it.  A window with up to four NaN yields its 5th smallest
+ * number, one with five or more yields NaN.  Sign of zero: -0 and +0 are equal in that order; where a window holds zeros of both
+ * signs and the median is a zero, only its value is defined, not its sign.  Everywhere else the result is defined to the bit. */
 int pdeip_median3_dev(void *stream, const float *A, const float *B, int nrows, int ncols, float *out);
 /* Two fields in one launch: out0 = medfilt2(A0 + B0), out1 = medfilt2(A1 + B1) (:352-353 filters U+dU and V+dV). */
 int pdeip_median3_pair_dev(void *stream, const float *A0, const float *B0, const float *A1, const float *B1, int nrows, int ncols,

@@ -163,7 +163,9 @@ def op_diff_weights(U, V, dU, dV):
 
 
 def median3_sum(A, B=None):
-    """medfilt2(A + B, [3 3], 'symmetric') (:352)."""
+    """medfilt2(A + B, [3 3], 'symmetric') (:352).  OUR definition where medfilt2's is not documented: the 5th of the nine
+    window values in ascending order with NaN as the largest value (np.sort's and MATLAB sort's order), so up to four NaN in a
+    window leave a number and five or more give NaN.  Which zero comes out of a window that holds -0 and +0 is unspecified."""
     S = A.astype(F32) if B is None else (A.astype(F32) + B.astype(F32)).astype(F32)
     P = np.pad(S, 1, mode="symmetric")
     nrows, ncols = S.shape
@@ -265,10 +267,21 @@ def _pad_edge(A):
     return np.pad(A, 1, mode="edge")
 
 
-def ad_diff_weights(D, quantile=None):
-    """[W NW N NE E SE S SW] = ADdiffWeights(D), double; D is [nrows, ncols(, F)] single.
-    quantile None: TVdenoise8.m:119-231 (lambda = median, outer rows/columns of the weights zeroed);
-    a number: FlowEminAD_llin_2D_v10.m:416-487 (lambda = sorted(round(numel*quantile)), circshift wrap-around kept)."""
+def matlab_max_index(A):
+    """The index of [~, ind] = max(A, [], 3), 0-based: max ignores NaN, so the first maximal number wins; a pixel that is NaN in
+    every frame gets frame 0 (MATLAB's index 1) and thereby NaN.  (np.argmax would pick the first NaN frame instead.)  A holds
+    squared norms: nothing in it is negative."""
+    nan = np.isnan(A)
+    return np.where(nan.all(axis=2), 0, np.argmax(np.where(nan, -np.inf, A), axis=2))
+
+
+def matlab_max(A):
+    """max(A, [], 3): NaN is ignored, the result is NaN only where every frame is.  (ndarray.max would propagate any NaN.)"""
+    return np.fmax.reduce(A, axis=2)
+
+
+def ad_frame_gradients(D):
+    """Dx, Dy = imfilter(double(D), O_dx / O_dy, 'replicate', 'conv') with the Alvarez operators, per frame: [nrows, ncols, F] double."""
     D = D.astype(np.float64)
     if D.ndim == 2:
         D = D[:, :, None]
@@ -292,24 +305,47 @@ def ad_diff_weights(D, quantile=None):
         dy = dy + (-k2) * at(-1, 0)
         dy = dy + (-k1) * at(-1, -1)
         gxs.append(dx); gys.append(dy)
-    gx, gy = np.stack(gxs, 2), np.stack(gys, 2)
-    nn = gx * gx + gy * gy
-    best = np.argmax(nn, axis=2)                       # first maximal frame, like MATLAB's max
+    return np.stack(gxs, 2), np.stack(gys, 2)
+
+
+def ad_strongest(gx, gy, best=None):
+    """maxDx, maxDy of the frame `best` per pixel (default: MATLAB's max over the squared norms) and normDxDy of that frame."""
+    nrows, ncols, _ = gx.shape
+    if best is None:
+        best = matlab_max_index(gx * gx + gy * gy)     # [~, Mind] = max(Dx.^2 + Dy.^2, [], 3)
     ii, jj = np.meshgrid(np.arange(nrows), np.arange(ncols), indexing="ij")
     mx, my = gx[ii, jj, best], gy[ii, jj, best]
-    norm = mx * mx + my * my
+    return mx, my, mx * mx + my * my
+
+
+def ad_sorted_nonzero(norm):
+    """sort(normDxDy(normDxDy ~= 0)): ascending, NaN (which is not equal to 0) last."""
     srt = np.sort(norm.ravel())
-    srt = srt[srt != 0]
+    return srt[srt != 0]
+
+
+def ad_rank(count, quantile=None):
+    """The 1-based index into the `count` sorted non-zero norms: round(count*0.5 + eps) for the TV denoiser's median (quantile
+    None), round(count*quantile) for the flow driver, not below 1."""
     if quantile is None:
-        lam = srt[(srt.size + 1) // 2 - 1] if srt.size else 1.0   # sorted(round(numel*0.5 + eps))
-    else:
-        lam = srt[max(int(np.floor(srt.size * quantile + 0.5)), 1) - 1] if srt.size else 1.0   # sorted(round(numel*quantile))
+        return (count + 1) // 2
+    return max(int(np.floor(count * quantile + 0.5)), 1)
+
+
+def ad_lambda(norm, quantile=None):
+    srt = ad_sorted_nonzero(norm)
+    return srt[ad_rank(srt.size, quantile) - 1] if srt.size else 1.0
+
+
+def ad_tensor_weights(mx, my, norm, lam, wrap):
+    """The eight weights from the strongest gradient and lambda; wrap: circshift's wrap-around kept (flow driver), otherwise the
+    outer rows / columns are zeroed (TV denoiser)."""
     multip = 1.0 / (norm + 2.0 * lam)
     dyy, dxx, dxy = multip * (my * my + lam), multip * (mx * mx + lam), -multip * (mx * my)
     sh = lambda A, di, dj: np.roll(np.roll(A, di, axis=0), dj, axis=1)
-    if quantile is not None:
+    if wrap:
         return [0.5 * (dyy + sh(dyy, 0, 1)), 0.25 * (dxy + sh(dxy, 1, 1)), 0.5 * (dxx + sh(dxx, 1, 0)), -0.25 * (dxy + sh(dxy, 1, -1)),
-                0.5 * (dyy + sh(dyy, 0, -1)), 0.25 * (dxy + sh(dxy, -1, -1)), 0.5 * (dxx + sh(dxx, -1, 0)), -0.25 * (dxy + sh(dxy, -1, 1))], lam
+                0.5 * (dyy + sh(dyy, 0, -1)), 0.25 * (dxy + sh(dxy, -1, -1)), 0.5 * (dxx + sh(dxx, -1, 0)), -0.25 * (dxy + sh(dxy, -1, 1))]
     W = 0.5 * (dyy + sh(dyy, 0, 1)); W[:, 0] = 0
     NW = 0.25 * (dxy + sh(dxy, 1, 1)); NW[:, 0] = 0; NW[0, :] = 0
     N = 0.5 * (dxx + sh(dxx, 1, 0)); N[0, :] = 0
@@ -318,7 +354,18 @@ def ad_diff_weights(D, quantile=None):
     SE = 0.25 * (dxy + sh(dxy, -1, -1)); SE[:, -1] = 0; SE[-1, :] = 0
     S = 0.5 * (dxx + sh(dxx, -1, 0)); S[-1, :] = 0
     SW = -0.25 * (dxy + sh(dxy, -1, 1)); SW[-1, :] = 0; SW[:, 0] = 0
-    return [W, NW, N, NE, E, SE, S, SW], lam
+    return [W, NW, N, NE, E, SE, S, SW]
+
+
+def ad_diff_weights(D, quantile=None):
+    """[W NW N NE E SE S SW] = ADdiffWeights(D), double; D is [nrows, ncols(, F)] single.
+    quantile None: TVdenoise8.m:119-231 (lambda = median, outer rows/columns of the weights zeroed);
+    a number: FlowEminAD_llin_2D_v10.m:416-487 (lambda = sorted(round(numel*quantile)), circshift wrap-around kept).
+    The strongest frame is MATLAB's max over the frames (NaN norms skipped; NaN only where every frame is NaN), and a NaN norm is
+    a non-zero one that sorts last."""
+    mx, my, norm = ad_strongest(*ad_frame_gradients(D))
+    lam = ad_lambda(norm, quantile)
+    return ad_tensor_weights(mx, my, norm, lam, wrap=quantile is not None), lam
 
 
 def tv_assemble(Iout, Iin, alpha):
@@ -681,7 +728,7 @@ def tv4_diff_weights(D):
     def w(di, dj, cross):
         a = (sh(D3, di, dj) - D3).astype(F32)
         b = (cross + sh(cross, di, dj)).astype(F32)
-        m = ((a * a).astype(F32) + (b * b).astype(F32)).astype(F32).max(axis=2)
+        m = matlab_max(((a * a).astype(F32) + (b * b).astype(F32)).astype(F32))   # max(w, [], 3) (:128-131)
         return (F32(1) / np.sqrt((m + F32(0.00001)).astype(F32))).astype(F32)
 
     wW, wE, wN, wS = w(0, 1, ver), w(0, -1, ver), w(1, 0, hor), w(-1, 0, hor)

@@ -304,9 +304,14 @@ __global__ void k_flow_opdiffweights(float *wW, float *wN, float *wS, float *wE,
 
 // medfilt2(A + B, [3 3], 'symmetric') (:352-353): exact selection of the 5th of 9, symmetric padding
 // (the edge pixel is mirrored, i.e. index -1 -> 0 and n -> n-1).
+// The order is that of an ascending sort with NaN as the largest value (above +Inf), as MATLAB's sort and numpy's place it:
+// a window with k NaN yields its 5th smallest number for k <= 4 and NaN for k >= 5.  (fminf / fmaxf would drop a NaN and
+// duplicate its partner.)  -0 and +0 compare equal and are not exchanged: which zero a window holding both signs yields is
+// not part of the contract (include/pdeip.h).
 __device__ __forceinline__ void cswap(float &a, float &b)
 {
-    const float lo = fminf(a, b), hi = fmaxf(a, b);
+    const bool exchange = (a > b) || (a != a); // a NaN in the low slot moves up; two NaN trade places, which changes nothing
+    const float lo = exchange ? b : a, hi = exchange ? a : b;
     a = lo;
     b = hi;
 }

@@ -17,8 +17,8 @@
 
 namespace pdeip {
 
-// Ddx, Ddy of the frame with the largest squared gradient norm (first frame on ties, like MATLAB's max),
-// and that norm.  Kernel elements in MATLAB order of the rotated kernel, zero taps skipped.
+// Ddx, Ddy of the frame with the largest squared gradient norm (first frame on ties, NaN norms skipped, frame 0 if every
+// norm is NaN: MATLAB's max), and that norm.  Kernel elements in MATLAB order of the rotated kernel, zero taps skipped.
 __global__ void k_tv_gradient(double *gx, double *gy, double *nrm, const float *D, int nrows, int ncols, int nframes)
 {
     PDEIP_PIXEL_INDEX();
@@ -27,7 +27,7 @@ __global__ void k_tv_gradient(double *gx, double *gy, double *nrm, const float *
     const double k1 = 1.0 / s, k2 = sqrt(2.0) / s; // [1 sqrt(2) 1] ./ (4+sqrt(8))
     auto ci = [&](int v) { return v < 0 ? 0 : (v > nrows - 1 ? nrows - 1 : v); };
     auto cj = [&](int v) { return v < 0 ? 0 : (v > ncols - 1 ? ncols - 1 : v); };
-    double bx = 0.0, by = 0.0, bn = -1.0;
+    double bx = 0.0, by = 0.0, bn = 0.0;
     for (int f = 0; f < nframes; ++f) {
         const float *P = D + (size_t)f * n;
         auto at = [&](int ii, int jj) { return (double)P[(size_t)cj(jj) * nrows + ci(ii)]; };
@@ -46,7 +46,9 @@ __global__ void k_tv_gradient(double *gx, double *gy, double *nrm, const float *
         dy = dy + (-k2) * at(i - 1, j);
         dy = dy + (-k1) * at(i - 1, j - 1);
         const double nn = dx * dx + dy * dy;
-        if (nn > bn) { // strictly greater: the first maximal frame wins
+        // [~, ind] = max(norms, [], 3): frame 0 first, then strictly greater (the first maximal frame wins) or the first number
+        // after NaN incumbents (max skips NaN); a pixel that is NaN in every frame keeps frame 0 and carries NaN on
+        if (f == 0 || nn > bn || (bn != bn && nn == nn)) {
             bn = nn;
             bx = dx;
             by = dy;
