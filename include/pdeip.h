@@ -906,6 +906,66 @@ int pdeip_disp_segmentation(const float *Din, int nrows, int ncols, const float 
                             const pdeip_dispseg_params *prm, unsigned long long seed, int *S_out, float *PHI_out, int *SEG_out,
                             float *surf_out);
 
+/* ---- the sparse driver (csrc/pdeip_sparse.hip, csrc/pdeip_segmentation.hip) ----------------------------------------------------
+ * DispSegmentationSparse.m takes disparity maps whose NaNs mean "no estimate".  It differs from the dense driver in nanmedfilt2(),
+ * in its D pyramid, in generateSeeds()'s starting gamma and in constants that are parameters of the stage calls above.
+ *
+ * out = nanmedfilt2(A) (DispSegmentationSparse.m:679-685: colfilt(A, [3 3], 'sliding', @nanmedian); the .m ignores its fsize
+ * argument).  This library's definition.  A, out column-major float32 [nrows x ncols x nframes], every plane filtered on its own.
+ *   The window of pixel (i, j) is its 3x3 neighbourhood; a position outside the plane contributes the VALUE 0.0f (colfilt's zero
+ * padding is a value, not a missing one).  NaNs in the window are ignored.  With n the number of non-NaN values among the nine:
+ *     n == 0   NaN (an edge pixel always sees at least three zeros and a corner five: this happens at interior pixels only)
+ *     n odd    the (n+1)/2-th smallest value
+ *     n even   (float)(((double)a + (double)b) * 0.5) of the n/2-th and (n/2+1)-th smallest: the correctly rounded mean, no overflow
+ *   +Inf and -Inf in the middle of an even window give NaN, two equal infinities that infinity.  -0 and +0 compare equal; which
+ * zero comes out of a window holding both is not part of the contract (compare by value), as for pdeip_median3_dev.  Everywhere
+ * else the result is defined to the bit.  out must not alias A.
+ *   Refused with PDEIP_ERR_ARG before any HIP call: a NULL pointer, nrows, ncols or nframes < 1, a plane of more than INT_MAX
+ * pixels, out == A; with PDEIP_ERR_UNSUPPORTED: more than 65535 columns or frames (the launch geometry).  The _dev form takes
+ * device pointers, is asynchronous on `stream`, one launch, reads nothing back: graph-capturable.  The host form copies A up and
+ * out down.  pdeip_set_mode does not apply. */
+int pdeip_nanmedfilt2_dev(void *stream, const float *A, int nrows, int ncols, int nframes, float *out);
+int pdeip_nanmedfilt2(const float *A, int nrows, int ncols, int nframes, float *out);
+/* The sparse driver's D pyramid (:63-64, :76-79), host pointers: P_1 = nanmedfilt2(D), P_{k+1} = nanmedfilt2(imresize(nanmedfilt2(
+ * P_k), scl_factor)), imresize being pdeip_pyr_resize_dev(cubic = 1) at ceil(size*scl_factor).  The sizes follow the rule of
+ * pdeip_region_competition with pyr_scl in place of rc_scl.  Where NaNs go in a resize is that call's definition: a NaN reaches
+ * every output pixel whose tap list touches it, zero-weight taps included.  3K - 2 launches, all on the device.
+ *   *K_out = K; sizes_out int [2*scales_cap] receives rows, cols per scale (2K entries); out receives the K planes packed in scale
+ * order without padding.  out == NULL: the sizes only, no HIP call, D is not read.  Refused with PDEIP_ERR_ARG before any HIP
+ * call: a NULL K_out or sizes_out, a NULL D with out given, nrows or ncols < 3, a plane of more than INT_MAX pixels, scl_factor
+ * outside (0, 1), pyr_scl not finite or <= 0, scales_cap < 1 or smaller than K (nothing is written then); PDEIP_ERR_UNSUPPORTED:
+ * more than 65535 columns. */
+int pdeip_sparse_pyramid(const float *D, int nrows, int ncols, double scl_factor, double pyr_scl, int scales_cap, int *K_out,
+                         int *sizes_out, float *out);
+/* generateSeeds() and regionCompetition() of DispSegmentationSparse.m (:207-447, :452-674): pdeip_generate_seeds and
+ * pdeip_region_competition, argument for argument, with three things different:
+ *   - D is the raw map with its NaNs; its pyramid is pdeip_sparse_pyramid's, built inside the call.  The filled copy of each scale
+ *     (nan_fill) is made from that pyramid (:287, :500).  The AA and PHI pyramids stay plain cubic resizes.
+ *   - a NaN member of prm, or prm == NULL, resolves to the SPARSE driver's value: seeds dist_cap 100, nan_fill 1000, mincov_gate
+ *     0.5; competition c0 2, c1 4, dh_floor 0.04, err_thr 1.2, gamma_coef 0.005, dist_cap 100, nan_fill 1000.  (A struct cannot ask
+ *     for "no fill" or "no gate" here: that is what the dense calls are for.)
+ *   - generateSeeds()'s gamma starts at 0.005 per call (:226).
+ * Everything else, the refusals included, is as stated for the dense calls. */
+int pdeip_generate_seeds_sparse(const float *D, const float *AA, int nrows, int ncols, int order, double sigmaLim, const double *cset_vect,
+                                int n_cset, int iterations, int seeds, double scl_factor, double pyr_scl, unsigned long long seed,
+                                unsigned long long *fit_counter, const pdeip_seeds_params *prm, pdeip_seeds_trace *trace, int *S_out,
+                                float *PHI_out, float *surf_out);
+int pdeip_region_competition_sparse(const float *D, const float *PHI, int nrows, int ncols, int S, int order, int strategy, double sigmaLim,
+                                    float ransac_cset, int iterations, double srem_thr, double scl_factor, double rc_scl,
+                                    unsigned long long seed, const pdeip_seg_params *prm, int *S_out, float *PHI_out, float *surf_out,
+                                    int *kept_out);
+/* [PHI SEG SParam] = DispSegmentationSparse(Din, param) (DispSegmentationSparse.m:42-202), host pointers: pdeip_disp_segmentation
+ * with Din's NaNs left in place (the stages filter them), the two sparse stage calls above, and the sparse .m's defaults for a NaN
+ * / 0 member of prm or prm == NULL: srem_thr 0.002, polyorder 2, seeds 15, scl_factor 0.75, gen_scl 0.55, rc_scl 0.55,
+ * ransac_min_cset 0.1, ransac_max_cset 0.7, ransac_cset_cycles 10.  The stage constants (0.7/20, 1.5/30, 1.2/20, 1.5/20; with
+ * PHIin 1.0/20, 1.2/20 with one seed, 2.0/20), the strategy (inverse), AA == 1 as the allowed area, the stage seeds, PHI crossing
+ * the host between stages, SEG through pdeip_seg_label, *S_out = 0 after a stage that leaves no segment, the sizes of the outputs
+ * and the refusals are those of pdeip_disp_segmentation.  The .m's param.varLim is never read and its `keyboard` block (:544-547)
+ * is a debugging stop.  Not graph-capturable. */
+int pdeip_disp_segmentation_sparse(const float *Din, int nrows, int ncols, const float *PHIin, int S_in, const float *AA,
+                                   const pdeip_dispseg_params *prm, unsigned long long seed, int *S_out, float *PHI_out, int *SEG_out,
+                                   float *surf_out);
+
 #ifdef __cplusplus
 }
 #endif

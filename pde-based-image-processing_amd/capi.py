@@ -159,6 +159,15 @@ SIGNATURES = {
     "pdeip_generate_seeds": [_P, _P, _I, _I, _I, ctypes.c_double, _P, _I, _I, _I, ctypes.c_double, ctypes.c_double, ctypes.c_ulonglong, _P, _P, _P,
                              _P, _P, _P],
     "pdeip_disp_segmentation": [_P, _I, _I, _P, _I, _P, _P, ctypes.c_ulonglong, _P, _P, _P, _P],
+    # the sparse driver (csrc/pdeip_sparse.hip, csrc/pdeip_segmentation.hip)
+    "pdeip_nanmedfilt2_dev": [_P, _P, _I, _I, _I, _P],
+    "pdeip_nanmedfilt2": [_P, _I, _I, _I, _P],
+    "pdeip_sparse_pyramid": [_P, _I, _I, ctypes.c_double, ctypes.c_double, _I, _P, _P, _P],
+    "pdeip_generate_seeds_sparse": [_P, _P, _I, _I, _I, ctypes.c_double, _P, _I, _I, _I, ctypes.c_double, ctypes.c_double, ctypes.c_ulonglong, _P,
+                                    _P, _P, _P, _P, _P],
+    "pdeip_region_competition_sparse": [_P, _P, _I, _I, _I, _I, _I, ctypes.c_double, _F, _I, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                        ctypes.c_ulonglong, _P, _P, _P, _P, _P],
+    "pdeip_disp_segmentation_sparse": [_P, _I, _I, _P, _I, _P, _P, ctypes.c_ulonglong, _P, _P, _P, _P],
     # library state
     "pdeip_set_mode": [_I],
     "pdeip_get_mode": [],

@@ -139,6 +139,10 @@ int check_deriv_dims(const char *who, int nrows, int ncols, int nframes);
 int copy_d2d(hipStream_t s, float *dst, const float *src, size_t n);
 inline dim3 pixel_grid(int nrows, int ncols, int nz) { return dim3((unsigned)((nrows + 255) / 256), (unsigned)ncols, (unsigned)nz); }
 
+// The sparse driver's D pyramid on device planes (pdeip_sparse.hip): P[0] = nanmed(D), P[k] = nanmed(resize_cubic(nanmed(P[k-1]))), 3K - 2
+// launches on s.  rc: rows, cols per scale [2K]; t1 / t2: a plane of scale 1 / scale 2 (sparse::layout of pdeip_sparse_plan.hpp).
+int sparse_pyramid_dev(hipStream_t s, const float *D, const int *rc, int K, float *const *P, float *t1, float *t2);
+
 // Makes group[0] (or `device`) the current HIP device; reads the environment knobs on first use.
 int use_device();
 int use_device(int device);

@@ -12,6 +12,7 @@
 
 #include "pdeip_models.hpp"
 #include "pdeip_pointwise.hpp"
+#include "pdeip_cswap.hpp"
 
 namespace pdeip {
 
@@ -308,13 +309,7 @@ __global__ void k_flow_opdiffweights(float *wW, float *wN, float *wS, float *wE,
 // a window with k NaN yields its 5th smallest number for k <= 4 and NaN for k >= 5.  (fminf / fmaxf would drop a NaN and
 // duplicate its partner.)  -0 and +0 compare equal and are not exchanged: which zero a window holding both signs yields is
 // not part of the contract (include/pdeip.h).
-__device__ __forceinline__ void cswap(float &a, float &b)
-{
-    const bool exchange = (a > b) || (a != a); // a NaN in the low slot moves up; two NaN trade places, which changes nothing
-    const float lo = exchange ? b : a, hi = exchange ? a : b;
-    a = lo;
-    b = hi;
-}
+// cswap: csrc/pdeip_cswap.hpp (shared with k_nanmedian3).
 
 // blockIdx.z = 1 filters the second field (out1 = medfilt2(A1 + B1)): the drivers filter U+dU and V+dV back to back
 __global__ void k_median3_sum(float *out, const float *A, const float *B, int nrows, int ncols, float *out1 = nullptr, const float *A1 = nullptr,

@@ -7,14 +7,20 @@
 //   the numbered segment map (DispSegmentation.m:190-198)                 pdeip_seg_label(_dev)
 //   generateSeeds() (DispSegmentation.m:203-443)                          pdeip_generate_seeds
 //   the dense driver (DispSegmentation.m:31-198)                          pdeip_disp_segmentation
+//   the sparse driver (DispSegmentationSparse.m:42-202) and its two stages    pdeip_disp_segmentation_sparse, pdeip_generate_seeds_sparse,
+//                                                                         pdeip_region_competition_sparse
+// Each dense / sparse pair shares one body: which builder makes the D pyramid, the constants a NaN member or a NULL struct resolves to
+// and generateSeeds()'s starting gamma are passed in (Form below).
 //
-// Kernels: csrc/pdeip_segmentation.hpp; the seed loop's host-side schedule: csrc/pdeip_seeds_plan.hpp; the contract: include/pdeip.h.  The fit is pdeip_surface_fit_masked_dev, the terms and the
+// Kernels: csrc/pdeip_segmentation.hpp; the seed loop's host-side schedule: csrc/pdeip_seeds_plan.hpp, the sparse forms' plan:
+// csrc/pdeip_sparse_plan.hpp (the pyramid itself: csrc/pdeip_sparse.hip); the contract: include/pdeip.h.  The fit is pdeip_surface_fit_masked_dev, the terms and the
 // step pdeip_cv_terms_dev / pdeip_cv_solver_dev.  pdeip_set_mode does not apply.
 //
 // Build (build.py): hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -c, one object per translation unit.
 #include "pdeip_ctx.hpp"
 #include "pdeip_segmentation.hpp"
 #include "pdeip_seeds_plan.hpp"
+#include "pdeip_sparse_plan.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -32,9 +38,10 @@ struct SegPrm {
     double gamma_coef, dist_cap;
     float nan_fill;
 };
-SegPrm seg_resolve(const pdeip_seg_params *u)
+SegPrm seg_resolve(const pdeip_seg_params *u, bool sparse = false)
 {
     SegPrm p{1.0f, 1.0f, 0.06f, 1.0f, 0.001, std::numeric_limits<double>::infinity(), std::numeric_limits<float>::quiet_NaN()}; // DispSegmentation.m
+    if (sparse) p = SegPrm{2.0f, 4.0f, 0.04f, 1.2f, 0.005, 100.0, 1000.0f}; // DispSegmentationSparse.m
     if (u) {
         if (!std::isnan(u->c0)) p.c0 = (float)u->c0;
         if (!std::isnan(u->c1)) p.c1 = (float)u->c1;
@@ -134,6 +141,46 @@ int pinned_sizes(int S, int **out)
     }
     *out = g_pinned;
     return PDEIP_OK;
+}
+
+// What the two drivers' stages differ in beyond their parameter structs.
+struct Form {
+    bool sparse;   // the D pyramid: plain cubic resizes of D, or nanmedfilt2 around every step (sparse_pyramid_dev)
+    double gamma0; // generateSeeds()'s starting gamma
+};
+constexpr Form DENSE_FORM{false, seeds::GAMMA0}, SPARSE_FORM{true, sparse::GAMMA0};
+
+// Floats the D pyramid's builder needs beside the K planes: none for the plain form, a staging plane for the raw D and the two
+// temporaries for the sparse one.
+template <class Sizes>
+size_t pyramid_extra(const Form &f, const Sizes &sz, int K)
+{
+    if (!f.sparse) return 0;
+    std::vector<seeds::Size> q;
+    for (int k = 0; k < K; k++) q.push_back(seeds::Size{sz[k].first, sz[k].second});
+    const sparse::Layout L = sparse::layout(q);
+    return pad4((size_t)q[0].r * q[0].c) + (L.total - L.t1);
+}
+
+// Uploads the host map D and fills Dp[0..K): the dense form as it always did, the sparse one through `extra`.
+template <class Sizes>
+int build_d_pyramid(const Form &f, hipStream_t s, const float *D, const Sizes &sz, int K, float *const *Dp, float *extra)
+{
+    const size_t n0 = (size_t)sz[0].first * sz[0].second;
+    if (!f.sparse) {
+        HIPCHK(hipMemcpy(Dp[0], D, n0 * sizeof(float), hipMemcpyHostToDevice));
+        for (int k = 1; k < K; k++)
+            RC(pdeip_pyr_resize_dev(s, Dp[k - 1], sz[k - 1].first, sz[k - 1].second, 1, sz[k].first, sz[k].second, 1, Dp[k]));
+        return PDEIP_OK;
+    }
+    std::vector<int> rc;
+    for (int k = 0; k < K; k++) {
+        rc.push_back(sz[k].first);
+        rc.push_back(sz[k].second);
+    }
+    float *t1 = extra + pad4(n0), *t2 = t1 + (K > 1 ? pad4(n0) : 0);
+    HIPCHK(hipMemcpy(extra, D, n0 * sizeof(float), hipMemcpyHostToDevice));
+    return sparse_pyramid_dev(s, extra, rc.data(), K, Dp, t1, t2);
 }
 
 } // namespace
@@ -341,14 +388,18 @@ extern "C" int pdeip_seg_competition_level(const float *PHI, const float *D, int
 }
 
 // ---- regionCompetition(): the D pyramid, the visits [1..K, K..1], PHI carried from visit to visit --------------------------------
-extern "C" int pdeip_region_competition(const float *D, const float *PHI, int nrows, int ncols, int S, int order, int strategy, double sigmaLim,
-                                        float ransac_cset, int iterations, double srem_thr, double scl_factor, double rc_scl, unsigned long long seed,
-                                        const pdeip_seg_params *prm, int *S_out, float *PHI_out, float *surf_out, int *kept_out)
+namespace {
+
+int region_competition(const char *who, const Form &form, const float *D, const float *PHI, int nrows, int ncols, int S, int order, int strategy,
+                       double sigmaLim, float ransac_cset, int iterations, double srem_thr, double scl_factor, double rc_scl,
+                       unsigned long long seed, const pdeip_seg_params *prm, int *S_out, float *PHI_out, float *surf_out, int *kept_out)
 {
-    const char *who = "pdeip_region_competition";
     tls.err[0] = '\0'; // a call that succeeds leaves pdeip_last_error() empty
     NONNULL(who, D); NONNULL(who, PHI); NONNULL(who, S_out); NONNULL(who, PHI_out); NONNULL(who, surf_out); NONNULL(who, kept_out);
-    const SegPrm p = seg_resolve(prm);
+    const SegPrm p = seg_resolve(prm, form.sparse);
+    // what every level call of this run resolves to: the dense form hands the caller's struct on as it is
+    const pdeip_seg_params full{p.c0, p.c1, p.dh_floor, p.err_thr, p.gamma_coef, p.dist_cap, p.nan_fill};
+    const pdeip_seg_params *level_prm = form.sparse ? &full : prm;
     RC(check_level(who, nrows, ncols, S, order, strategy, sigmaLim, ransac_cset, iterations, srem_thr, p));
     if (!(scl_factor > 0.0 && scl_factor < 1.0)) return set_err(PDEIP_ERR_ARG, "%s: scl_factor must lie in (0, 1) (got %g)", who, scl_factor);
     if (!(rc_scl > 0.0) || !std::isfinite(rc_scl)) return set_err(PDEIP_ERR_ARG, "%s: rc_scl must be finite and > 0 (got %g)", who, rc_scl);
@@ -367,7 +418,7 @@ extern "C" int pdeip_region_competition(const float *D, const float *PHI, int nr
     size_t nD = 0;
     for (auto &q : sz) nD += pad4((size_t)q.first * q.second);
     float *ws = nullptr;
-    RC(ws_get(WS_SEG_RC, (nD + 2 * nS + pad4((size_t)S * ncoef)) * sizeof(float), &ws));
+    RC(ws_get(WS_SEG_RC, (nD + 2 * nS + pad4((size_t)S * ncoef) + pyramid_extra(form, sz, K)) * sizeof(float), &ws));
     std::vector<float *> Dp((size_t)K);
     float *at = ws;
     for (int k = 0; k < K; k++) {
@@ -375,10 +426,8 @@ extern "C" int pdeip_region_competition(const float *D, const float *PHI, int nr
         at += pad4((size_t)sz[k].first * sz[k].second);
     }
     float *A = at, *B = A + nS, *dM = B + nS;
-    HIPCHK(hipMemcpy(Dp[0], D, n0 * sizeof(float), hipMemcpyHostToDevice));
+    RC(build_d_pyramid(form, nullptr, D, sz, K, Dp.data(), dM + pad4((size_t)S * ncoef)));
     HIPCHK(hipMemcpy(A, PHI, n0 * S * sizeof(float), hipMemcpyHostToDevice));
-    for (int k = 1; k < K; k++)
-        RC(pdeip_pyr_resize_dev(nullptr, Dp[k - 1], sz[k - 1].first, sz[k - 1].second, 1, sz[k].first, sz[k].second, 1, Dp[k]));
 
     std::vector<int> visits;
     for (int k = 0; k < K; k++) visits.push_back(k);
@@ -390,8 +439,8 @@ extern "C" int pdeip_region_competition(const float *D, const float *PHI, int nr
     for (size_t v = 0; v < visits.size(); v++) {
         const int k = visits[v], r = sz[k].first, c = sz[k].second;
         int out = 0;
-        RC(pdeip_seg_competition_level_dev(nullptr, A, Dp[k], r, c, live, order, strategy, sigmaLim, ransac_cset, iterations, srem_thr, seed, &fit, prm,
-                                           &out, B, dM, kv.data(), nullptr));
+        RC(pdeip_seg_competition_level_dev(nullptr, A, Dp[k], r, c, live, order, strategy, sigmaLim, ransac_cset, iterations, srem_thr, seed, &fit,
+                                           level_prm, &out, B, dM, kv.data(), nullptr));
         for (int i = 0; i < out; i++) kept[i] = kept[kv[i]];
         live = out;
         if (live == 0) break;
@@ -411,6 +460,25 @@ extern "C" int pdeip_region_competition(const float *D, const float *PHI, int nr
     return PDEIP_OK;
 }
 
+} // namespace
+
+extern "C" int pdeip_region_competition(const float *D, const float *PHI, int nrows, int ncols, int S, int order, int strategy, double sigmaLim,
+                                        float ransac_cset, int iterations, double srem_thr, double scl_factor, double rc_scl, unsigned long long seed,
+                                        const pdeip_seg_params *prm, int *S_out, float *PHI_out, float *surf_out, int *kept_out)
+{
+    return region_competition("pdeip_region_competition", DENSE_FORM, D, PHI, nrows, ncols, S, order, strategy, sigmaLim, ransac_cset, iterations,
+                              srem_thr, scl_factor, rc_scl, seed, prm, S_out, PHI_out, surf_out, kept_out);
+}
+
+extern "C" int pdeip_region_competition_sparse(const float *D, const float *PHI, int nrows, int ncols, int S, int order, int strategy,
+                                               double sigmaLim, float ransac_cset, int iterations, double srem_thr, double scl_factor,
+                                               double rc_scl, unsigned long long seed, const pdeip_seg_params *prm, int *S_out, float *PHI_out,
+                                               float *surf_out, int *kept_out)
+{
+    return region_competition("pdeip_region_competition_sparse", SPARSE_FORM, D, PHI, nrows, ncols, S, order, strategy, sigmaLim, ransac_cset,
+                              iterations, srem_thr, scl_factor, rc_scl, seed, prm, S_out, PHI_out, surf_out, kept_out);
+}
+
 // ---- generateSeeds() (DispSegmentation.m:203-443): seed after seed, each grown over the visits [1..K, K..1] -----------------------
 namespace {
 
@@ -422,18 +490,16 @@ int check_seeds(const char *who, int nrows, int ncols, int order, double sigmaLi
     return bad ? set_err(PDEIP_ERR_ARG, "%s: %s", who, bad) : PDEIP_OK;
 }
 
-} // namespace
-
-extern "C" int pdeip_generate_seeds(const float *D, const float *AA, int nrows, int ncols, int order, double sigmaLim, const double *cset_vect,
-                                    int n_cset, int iterations, int n_seeds, double scl_factor, double pyr_scl, unsigned long long seed,
-                                    unsigned long long *fit_counter, const pdeip_seeds_params *prm, pdeip_seeds_trace *trace, int *S_out,
-                                    float *PHI_out, float *surf_out)
+int generate_seeds(const char *who, const Form &form, const float *D, const float *AA, int nrows, int ncols, int order, double sigmaLim,
+                   const double *cset_vect, int n_cset, int iterations, int n_seeds, double scl_factor, double pyr_scl, unsigned long long seed,
+                   unsigned long long *fit_counter, const pdeip_seeds_params *prm, pdeip_seeds_trace *trace, int *S_out, float *PHI_out,
+                   float *surf_out)
 {
-    const char *who = "pdeip_generate_seeds";
     tls.err[0] = '\0'; // a call that succeeds leaves pdeip_last_error() empty
     NONNULL(who, D); NONNULL(who, S_out); NONNULL(who, PHI_out); NONNULL(who, surf_out);
     RC(check_seeds(who, nrows, ncols, order, sigmaLim, cset_vect, n_cset, iterations, n_seeds, scl_factor, pyr_scl));
-    const seeds::Prm p = seeds::resolve(prm ? &prm->dist_cap : nullptr, prm ? &prm->nan_fill : nullptr, prm ? &prm->mincov_gate : nullptr);
+    const seeds::Prm p = sparse::resolve(form.sparse ? sparse::seeds_defaults() : sparse::dense_seeds_defaults(), prm ? &prm->dist_cap : nullptr,
+                                         prm ? &prm->nan_fill : nullptr, prm ? &prm->mincov_gate : nullptr);
     const std::vector<seeds::Size> sz = seeds::scale_sizes(nrows, ncols, scl_factor, pyr_scl);
     const int K = (int)sz.size(), ncoef = order == 1 ? 3 : 6;
     const bool fill = !std::isnan(p.nan_fill);
@@ -444,7 +510,9 @@ extern "C" int pdeip_generate_seeds(const float *D, const float *AA, int nrows, 
     for (auto &q : sz) nD += pad4((size_t)q.r * q.c);
     // workspace: cov (a double) first, then the count, the model, the pyramids of D, of D without NaNs and of AA, six planes
     float *ws = nullptr;
-    RC(ws_get(WS_SEEDS, (4 + 4 + 8 + (fill ? 3 : 2) * nD + 6 * nP) * sizeof(float), &ws));
+    std::vector<std::pair<int, int>> szp;
+    for (auto &q : sz) szp.push_back({q.r, q.c});
+    RC(ws_get(WS_SEEDS, (4 + 4 + 8 + (fill ? 3 : 2) * nD + 6 * nP + pyramid_extra(form, szp, K)) * sizeof(float), &ws));
     double *cov = reinterpret_cast<double *>(ws);
     int *cnt = reinterpret_cast<int *>(ws + 4);
     float *M = ws + 8, *at = M + 8;
@@ -461,14 +529,13 @@ extern "C" int pdeip_generate_seeds(const float *D, const float *AA, int nrows, 
     double *psum = nullptr;
     int *pcnt = nullptr;
 
-    HIPCHK(hipMemcpy(Dp[0], D, n0 * sizeof(float), hipMemcpyHostToDevice));
+    RC(build_d_pyramid(form, s, D, szp, K, Dp.data(), DIST + nP));
     {
         std::vector<float> a(n0, 1.0f); // AA{1}: all ones, or the caller's with its NaNs counted as 0
         if (AA)
             for (size_t i = 0; i < n0; i++) a[i] = AA[i] != AA[i] ? 0.0f : AA[i];
         HIPCHK(hipMemcpy(Ap[0], a.data(), n0 * sizeof(float), hipMemcpyHostToDevice));
     }
-    for (int k = 1; k < K; k++) RC(pdeip_pyr_resize_dev(s, Dp[k - 1], sz[k - 1].r, sz[k - 1].c, 1, sz[k].r, sz[k].c, 1, Dp[k]));
     for (int k = 0; k < K; k++) {
         if (!fill) { Df[(size_t)k] = Dp[(size_t)k]; continue; }
         const int npix = sz[k].r * sz[k].c;
@@ -478,7 +545,7 @@ extern "C" int pdeip_generate_seeds(const float *D, const float *AA, int nrows, 
 
     if (trace) trace->n_counts = trace->n_largest = 0;
     const size_t nK = (size_t)sz[K - 1].r * sz[K - 1].c;
-    double gamma = seeds::GAMMA0;
+    double gamma = form.gamma0;
     unsigned long long fit = fit_counter ? *fit_counter : 0ull;
     int S = 0;
     for (int sd = 0; sd < n_seeds; sd++) {
@@ -555,15 +622,37 @@ extern "C" int pdeip_generate_seeds(const float *D, const float *AA, int nrows, 
     return PDEIP_OK;
 }
 
-// ---- [PHI SEG SParam] = DispSegmentation(Din, param) (DispSegmentation.m:31-198) ------------------------------------------------
-extern "C" int pdeip_disp_segmentation(const float *Din, int nrows, int ncols, const float *PHIin, int S_in, const float *AA,
-                                       const pdeip_dispseg_params *prm, unsigned long long seed, int *S_out, float *PHI_out, int *SEG_out,
-                                       float *surf_out)
+} // namespace
+
+extern "C" int pdeip_generate_seeds(const float *D, const float *AA, int nrows, int ncols, int order, double sigmaLim, const double *cset_vect,
+                                    int n_cset, int iterations, int n_seeds, double scl_factor, double pyr_scl, unsigned long long seed,
+                                    unsigned long long *fit_counter, const pdeip_seeds_params *prm, pdeip_seeds_trace *trace, int *S_out,
+                                    float *PHI_out, float *surf_out)
 {
-    const char *who = "pdeip_disp_segmentation";
+    return generate_seeds("pdeip_generate_seeds", DENSE_FORM, D, AA, nrows, ncols, order, sigmaLim, cset_vect, n_cset, iterations, n_seeds, scl_factor,
+                          pyr_scl, seed, fit_counter, prm, trace, S_out, PHI_out, surf_out);
+}
+
+extern "C" int pdeip_generate_seeds_sparse(const float *D, const float *AA, int nrows, int ncols, int order, double sigmaLim,
+                                           const double *cset_vect, int n_cset, int iterations, int n_seeds, double scl_factor, double pyr_scl,
+                                           unsigned long long seed, unsigned long long *fit_counter, const pdeip_seeds_params *prm,
+                                           pdeip_seeds_trace *trace, int *S_out, float *PHI_out, float *surf_out)
+{
+    return generate_seeds("pdeip_generate_seeds_sparse", SPARSE_FORM, D, AA, nrows, ncols, order, sigmaLim, cset_vect, n_cset, iterations, n_seeds,
+                          scl_factor, pyr_scl, seed, fit_counter, prm, trace, S_out, PHI_out, surf_out);
+}
+
+// ---- [PHI SEG SParam] = DispSegmentation(Din, param) (DispSegmentation.m:31-198) ------------------------------------------------
+// The sparse driver (DispSegmentationSparse.m:42-202) is the same sequence of stages with its own defaults, Din's NaNs left in place
+// and the sparse stage calls.
+namespace {
+
+int disp_segmentation(const char *who, bool sparse_form, const float *Din, int nrows, int ncols, const float *PHIin, int S_in, const float *AA,
+                      const pdeip_dispseg_params *prm, unsigned long long seed, int *S_out, float *PHI_out, int *SEG_out, float *surf_out)
+{
     tls.err[0] = '\0';
     NONNULL(who, Din); NONNULL(who, S_out); NONNULL(who, PHI_out); NONNULL(who, SEG_out); NONNULL(who, surf_out);
-    seeds::DriverPrm p = seeds::driver_defaults();
+    seeds::DriverPrm p = sparse_form ? sparse::driver_defaults() : seeds::driver_defaults();
     if (prm) {
         if (!std::isnan(prm->srem_thr)) p.srem_thr = prm->srem_thr;
         if (!std::isnan(prm->scl_factor)) p.scl_factor = prm->scl_factor;
@@ -584,29 +673,32 @@ extern "C" int pdeip_disp_segmentation(const float *Din, int nrows, int ncols, c
     const std::vector<double> cset = seeds::cset_vector(p.ransac_min_cset, p.ransac_max_cset, p.ransac_cset_cycles);
     const int cap = PHIin ? S_in + 1 : 2 * p.seeds;
     RC(check_seeds(who, nrows, ncols, p.polyorder, 0.7, cset.data(), (int)cset.size(), 20, std::max(cap, 1), p.scl_factor, p.gen_scl));
-    const SegPrm dense = seg_resolve(nullptr);
-    RC(check_level(who, nrows, ncols, cap, p.polyorder, PDEIP_SEG_INVERSE, 1.0, (float)p.ransac_max_cset, 20, p.srem_thr, dense));
+    const SegPrm stage_prm = seg_resolve(nullptr, sparse_form);
+    RC(check_level(who, nrows, ncols, cap, p.polyorder, PDEIP_SEG_INVERSE, 1.0, (float)p.ransac_max_cset, 20, p.srem_thr, stage_prm));
+    const auto compete_call = sparse_form ? pdeip_region_competition_sparse : pdeip_region_competition;
+    const auto seeds_call = sparse_form ? pdeip_generate_seeds_sparse : pdeip_generate_seeds;
 
     const size_t n0 = (size_t)nrows * ncols;
     const int ncoef = p.polyorder == 1 ? 3 : 6;
     std::vector<float> Dz(Din, Din + n0), A(n0), P((size_t)cap * n0), Q((size_t)cap * n0);
     std::vector<int> kept((size_t)cap);
-    for (auto &d : Dz)
-        if (d != d) d = 0.0f; // we don't like NaNs (:61)
+    if (!sparse_form)
+        for (auto &d : Dz)
+            if (d != d) d = 0.0f; // we don't like NaNs (:61); the sparse driver filters them inside its stages (:63-64)
     int live = 0, stage = 0;
     *S_out = 0;
     auto compete = [&](double sigmaLim, int iterations) -> int { // P -> P
         int out = 0;
-        RC(pdeip_region_competition(Dz.data(), P.data(), nrows, ncols, live, p.polyorder, PDEIP_SEG_INVERSE, sigmaLim, (float)p.ransac_max_cset,
-                                    iterations, p.srem_thr, p.scl_factor, p.rc_scl, seeds::stage_seed(seed, stage++), nullptr, &out, Q.data(),
-                                    surf_out, kept.data()));
+        RC(compete_call(Dz.data(), P.data(), nrows, ncols, live, p.polyorder, PDEIP_SEG_INVERSE, sigmaLim, (float)p.ransac_max_cset,
+                                    iterations, p.srem_thr,
+                         p.scl_factor, p.rc_scl, seeds::stage_seed(seed, stage++), nullptr, &out, Q.data(), surf_out, kept.data()));
         live = out;
         std::swap(P, Q);
         return PDEIP_OK;
     };
     auto more_seeds = [&](double sigmaLim, const float *allowed, int n, double pyr_scl) -> int { // appends to P
         int out = 0;
-        RC(pdeip_generate_seeds(Dz.data(), allowed, nrows, ncols, p.polyorder, sigmaLim, cset.data(), (int)cset.size(), 20, n, p.scl_factor, pyr_scl,
+        RC(seeds_call(Dz.data(), allowed, nrows, ncols, p.polyorder, sigmaLim, cset.data(), (int)cset.size(), 20, n, p.scl_factor, pyr_scl,
                                 seeds::stage_seed(seed, stage++), nullptr, nullptr, nullptr, &out, P.data() + (size_t)live * n0,
                                 surf_out + (size_t)live * ncoef));
         live += out;
@@ -648,4 +740,21 @@ extern "C" int pdeip_disp_segmentation(const float *Din, int nrows, int ncols, c
     RC(pdeip_seg_label(PHI_out, nrows, ncols, live, SEG_out));
     *S_out = live;
     return PDEIP_OK;
+}
+
+} // namespace
+
+extern "C" int pdeip_disp_segmentation(const float *Din, int nrows, int ncols, const float *PHIin, int S_in, const float *AA,
+                                       const pdeip_dispseg_params *prm, unsigned long long seed, int *S_out, float *PHI_out, int *SEG_out,
+                                       float *surf_out)
+{
+    return disp_segmentation("pdeip_disp_segmentation", false, Din, nrows, ncols, PHIin, S_in, AA, prm, seed, S_out, PHI_out, SEG_out, surf_out);
+}
+
+extern "C" int pdeip_disp_segmentation_sparse(const float *Din, int nrows, int ncols, const float *PHIin, int S_in, const float *AA,
+                                              const pdeip_dispseg_params *prm, unsigned long long seed, int *S_out, float *PHI_out, int *SEG_out,
+                                              float *surf_out)
+{
+    return disp_segmentation("pdeip_disp_segmentation_sparse", true, Din, nrows, ncols, PHIin, S_in, AA, prm, seed, S_out, PHI_out, SEG_out,
+                             surf_out);
 }

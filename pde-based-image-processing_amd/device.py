@@ -355,6 +355,19 @@ def median3_pair(A0, B0, out0, A1, B1, out1):
     capi.call("pdeip_median3_pair_dev", _stream(), *_p(A0, B0, A1, B1), nrows, ncols, *_p(out0, out1))
 
 
+def nanmedfilt2(A, out=None):
+    """out = nanmedfilt2(A) of DispSegmentationSparse.m (colfilt(A, [3 3], 'sliding', @nanmedian): the NaN-ignoring 3x3 median with
+    zero padding; pdeip_nanmedfilt2_dev): A [(F,) ncols, nrows], every plane on its own; out like A, not A itself.  Returns out."""
+    if out is None:
+        out = torch.empty_like(A)
+    _chk(A, out)
+    if out.shape != A.shape:
+        raise capi.PdeipError(capi.PDEIP_ERR_ARG, "nanmedfilt2: out must have A's shape")
+    nrows, ncols, F = _dims(A)
+    capi.call("pdeip_nanmedfilt2_dev", _stream(), A.data_ptr(), nrows, ncols, F, out.data_ptr())
+    return out
+
+
 def disp_assemble(term1, term2, dU, alpha, CuGd, DuGd):
     """term = (It, Ix, b); term2 may be None (DispEminND_llin_2D.m:258-293) or the gradient-magnitude term (Ixt, Iyt, Ixx, Ixy, b)."""
     It1, Ix1, b1 = term1

@@ -531,8 +531,22 @@ def regionCompetition(D, PHI, polyorder, sigmaLim, ransac_cset, iterations, srem
     of matlab/segmentation/DispSegmentation.m (sparse=True: DispSegmentationSparse.m's constants) in one pdeip_region_competition
     call: the D pyramid (scl_factor, rc_scl as the drivers' param struct names them), the visits down and up, every iteration
     resident.  param overrides single constants (c0, c1, dh_floor, err_thr, gamma_coef, dist_cap, nan_fill).  Returns (PHI [rows,
-    cols, S_out], SParam [ncoef, S_out], kept: the 0-based input index of each surviving segment)."""
-    prm = dev.SegParams.make(sparse=sparse, **param)
+    cols, S_out], SParam [ncoef, S_out], kept: the 0-based input index of each surviving segment).
+    The sparse driver's own function, nanmedfilt2 pyramid included, is regionCompetitionSparse."""
+    return _region_competition("pdeip_region_competition", dev.SegParams.make(sparse=sparse, **param), D, PHI, polyorder, sigmaLim, ransac_cset,
+                               iterations, srem_thr, competition, seed, scl_factor, rc_scl)
+
+
+def regionCompetitionSparse(D, PHI, polyorder, sigmaLim, ransac_cset, iterations, srem_thr, competition="inverse", seed=0, scl_factor=0.75,
+                            rc_scl=0.55, **param):
+    """regionCompetition() of matlab/segmentation/DispSegmentationSparse.m in one pdeip_region_competition_sparse call: D is the raw
+    map with its NaNs, its pyramid is the sparse one (sparse_pyramid), the constants are the sparse driver's unless param overrides
+    one.  Arguments and result as regionCompetition."""
+    return _region_competition("pdeip_region_competition_sparse", dev.SegParams.make(**param), D, PHI, polyorder, sigmaLim, ransac_cset,
+                               iterations, srem_thr, competition, seed, scl_factor, rc_scl)
+
+
+def _region_competition(entry, prm, D, PHI, polyorder, sigmaLim, ransac_cset, iterations, srem_thr, competition, seed, scl_factor, rc_scl):
     Dm = np.asfortranarray(np.asarray(D, dtype=np.float32))
     P = _planes3(PHI)
     rows, cols, S = P.shape
@@ -543,7 +557,7 @@ def regionCompetition(D, PHI, polyorder, sigmaLim, ransac_cset, iterations, srem
     surf = np.zeros((ncoef, S), np.float32, order="F")
     kept = (ctypes.c_int * S)()
     s_out = ctypes.c_int(0)
-    capi.call("pdeip_region_competition", Dm.ctypes.data, P.ctypes.data, rows, cols, S, int(polyorder), dev._strategy(competition),
+    capi.call(entry, Dm.ctypes.data, P.ctypes.data, rows, cols, S, int(polyorder), dev._strategy(competition),
               float(sigmaLim), float(ransac_cset), int(iterations), float(srem_thr), float(scl_factor), float(rc_scl),
               ctypes.c_ulonglong(int(seed) & ((1 << 64) - 1)), ctypes.addressof(prm), ctypes.addressof(s_out), out.ctypes.data,
               surf.ctypes.data, ctypes.addressof(kept))
@@ -599,8 +613,23 @@ def generateSeeds(D, polyorder, sigmaLim, cset_vect, iterations, AA=None, seeds=
     matlab/segmentation/DispSegmentation.m (sparse=True: DispSegmentationSparse.m's constants dist_cap 100, nan_fill 1000,
     mincov_gate 0.5) in one pdeip_generate_seeds call; the pyramid is given by scl_factor and pyr_scl (the drivers' gen_scl or
     rc_scl).  param overrides single constants.  trace: a dict that receives counts (every count read back), largest (the v = K
-    largest-component planes [rK, cK, n]) and fit_counter.  Returns (PHI [rows, cols, S_out], SParam [ncoef, S_out])."""
+    largest-component planes [rK, cK, n]) and fit_counter.  Returns (PHI [rows, cols, S_out], SParam [ncoef, S_out]).
+    The sparse driver's own function, nanmedfilt2 pyramid and starting gamma included, is generateSeedsSparse."""
     vals = dict(dist_cap=100.0, nan_fill=1000.0, mincov_gate=0.5) if sparse else {}
+    return _generate_seeds("pdeip_generate_seeds", vals, D, polyorder, sigmaLim, cset_vect, iterations, AA, seeds, seed, scl_factor, pyr_scl,
+                           fit_counter, trace, param)
+
+
+def generateSeedsSparse(D, polyorder, sigmaLim, cset_vect, iterations, AA=None, seeds=15, seed=0, scl_factor=0.75, pyr_scl=0.55, fit_counter=0,
+                        trace=None, **param):
+    """generateSeeds() of matlab/segmentation/DispSegmentationSparse.m in one pdeip_generate_seeds_sparse call: D is the raw map with
+    its NaNs, its pyramid is the sparse one (sparse_pyramid), gamma starts at 0.005, the constants are the sparse driver's unless
+    param overrides one.  Arguments and result as generateSeeds."""
+    return _generate_seeds("pdeip_generate_seeds_sparse", {}, D, polyorder, sigmaLim, cset_vect, iterations, AA, seeds, seed, scl_factor,
+                           pyr_scl, fit_counter, trace, param)
+
+
+def _generate_seeds(entry, vals, D, polyorder, sigmaLim, cset_vect, iterations, AA, seeds, seed, scl_factor, pyr_scl, fit_counter, trace, param):
     for k, v in param.items():
         if k not in dict(_SeedsParams._fields_):
             raise TypeError("unknown generateSeeds parameter %r" % k)
@@ -629,7 +658,7 @@ def generateSeeds(D, polyorder, sigmaLim, cset_vect, iterations, AA=None, seeds=
         counts = np.zeros(cap, np.int32)
         largest = np.zeros(rows * cols * n, np.float32)  # no scale is larger than the first
         tr = _SeedsTrace(counts.ctypes.data, cap, 0, largest.ctypes.data, 0)
-    capi.call("pdeip_generate_seeds", Dm.ctypes.data, None if Am is None else Am.ctypes.data, rows, cols, int(polyorder), float(sigmaLim),
+    capi.call(entry, Dm.ctypes.data, None if Am is None else Am.ctypes.data, rows, cols, int(polyorder), float(sigmaLim),
               cs.ctypes.data, int(cs.size), iterations, seeds, float(scl_factor), float(pyr_scl),
               ctypes.c_ulonglong(int(seed) & ((1 << 64) - 1)), ctypes.addressof(fit), ctypes.addressof(prm),
               None if tr is None else ctypes.addressof(tr), ctypes.addressof(s_out), out.ctypes.data, surf.ctypes.data)
@@ -648,27 +677,38 @@ def DispSegmentation(Din, seed=0, PHI=None, AA=None, **param):
     call.  param: the .m's fields srem_thr, polyorder, seeds, scl_factor, gen_scl, rc_scl, ransac_min_cset, ransac_max_cset,
     ransac_cset_cycles (defaults as there); PHI (param.PHI) and AA (param.AA) as keywords.  Returns (PHI [rows, cols, S], SEG int32
     [rows, cols], SParam [ncoef, S]); with no segment left: S = 0 and SEG all zero."""
+    return _disp_segmentation("pdeip_disp_segmentation", "DispSegmentation", 1, Din, seed, PHI, AA, param)
+
+
+def DispSegmentationSparse(Din, seed=0, PHI=None, AA=None, **param):
+    """[PHI SEG SParam] = DispSegmentationSparse(Din, param) of matlab/segmentation/DispSegmentationSparse.m in one
+    pdeip_disp_segmentation_sparse call: Din's NaNs mean "no estimate" and stay in place.  param, PHI, AA and the result as
+    DispSegmentation, the defaults as the sparse .m has them (polyorder 2, scl_factor 0.75, gen_scl 0.55, rc_scl 0.55)."""
+    return _disp_segmentation("pdeip_disp_segmentation_sparse", "DispSegmentationSparse", 2, Din, seed, PHI, AA, param)
+
+
+def _disp_segmentation(entry, name, default_order, Din, seed, PHI, AA, param):
     names = dict(_DispSegParams._fields_)
     for k in param:
         if k not in names:
-            raise TypeError("unknown DispSegmentation parameter %r" % k)
+            raise TypeError("unknown %s parameter %r" % (name, k))
     prm = _DispSegParams(*[(float(param.get(k, float("nan"))) if t is ctypes.c_double else int(param.get(k, 0))) for k, t in _DispSegParams._fields_])
     Dm = np.asfortranarray(np.asarray(Din, dtype=np.float32))
     if Dm.ndim != 2:
-        raise ValueError("DispSegmentation: Din must be two-dimensional (got %s)" % (Dm.shape,))
+        raise ValueError(name + ": Din must be two-dimensional (got %s)" % (Dm.shape,))
     rows, cols = Dm.shape
     Pm, S_in = None, 0
     if PHI is not None:
         Pm = _planes3(PHI)
         S_in = Pm.shape[2]
         if Pm.shape[:2] != Dm.shape:
-            raise ValueError("DispSegmentation: PHI is %s but Din is %s" % (Pm.shape, Dm.shape))
+            raise ValueError("%s: PHI is %s but Din is %s" % (name, Pm.shape, Dm.shape))
     Am = None
     if AA is not None:
         Am = np.asfortranarray(np.asarray(AA, dtype=np.float32))
         if Am.shape != Dm.shape:
-            raise ValueError("DispSegmentation: AA is %s but Din is %s" % (Am.shape, Dm.shape))
-    polyorder = int(param.get("polyorder", 0)) or 1  # 0 keeps the .m's default, as in the C call
+            raise ValueError("%s: AA is %s but Din is %s" % (name, Am.shape, Dm.shape))
+    polyorder = int(param.get("polyorder", 0)) or default_order  # 0 keeps the .m's default, as in the C call
     n_seeds = int(param.get("seeds", 0)) or 15
     cap = max(S_in + 1 if Pm is not None else 2 * n_seeds, 1)
     ncoef = 6 if polyorder == 2 else 3
@@ -676,8 +716,44 @@ def DispSegmentation(Din, seed=0, PHI=None, AA=None, **param):
     surf = np.zeros((ncoef, cap), np.float32, order="F")
     SEG = np.zeros((rows, cols), np.int32, order="F")
     s_out = ctypes.c_int(0)
-    capi.call("pdeip_disp_segmentation", Dm.ctypes.data, rows, cols, None if Pm is None else Pm.ctypes.data, S_in,
+    capi.call(entry, Dm.ctypes.data, rows, cols, None if Pm is None else Pm.ctypes.data, S_in,
               None if Am is None else Am.ctypes.data, ctypes.addressof(prm), ctypes.c_ulonglong(int(seed) & ((1 << 64) - 1)),
               ctypes.addressof(s_out), out.ctypes.data, SEG.ctypes.data, surf.ctypes.data)
     k = s_out.value
     return np.asfortranarray(out[:, :, :k]), SEG, np.asfortranarray(surf[:, :k])
+
+
+def nanmedfilt2(D):
+    """D = nanmedfilt2(D) of matlab/segmentation/DispSegmentationSparse.m:679-685 (colfilt(D, [3 3], 'sliding', @nanmedian)) in one
+    pdeip_nanmedfilt2 call: the NaN-ignoring median of each 3x3 window, the positions outside the plane holding the value 0; even
+    counts give the mean of the two middle values, a window of nine NaNs gives NaN.  D [rows, cols] or [rows, cols, F]."""
+    Dm = np.asfortranarray(np.asarray(D, dtype=np.float32))
+    if Dm.ndim not in (2, 3):
+        raise ValueError("nanmedfilt2: D must be [rows, cols] or [rows, cols, F] (got %s)" % (Dm.shape,))
+    out = np.empty(Dm.shape, np.float32, order="F")
+    capi.call("pdeip_nanmedfilt2", Dm.ctypes.data, Dm.shape[0], Dm.shape[1], Dm.shape[2] if Dm.ndim == 3 else 1, out.ctypes.data)
+    return out
+
+
+def sparse_pyramid(D, scl_factor=0.75, pyr_scl=0.55):
+    """The D pyramid of DispSegmentationSparse.m:63-79 in one pdeip_sparse_pyramid call: P[0] = nanmedfilt2(D), P[k+1] =
+    nanmedfilt2(imresize(nanmedfilt2(P[k]), scl_factor)), down to the last scale with both sides >= pyr_scl x the original.
+    Returns the list of the scales' arrays."""
+    Dm = np.asfortranarray(np.asarray(D, dtype=np.float32))
+    if Dm.ndim != 2:
+        raise ValueError("sparse_pyramid: D must be two-dimensional (got %s)" % (Dm.shape,))
+    rows, cols = Dm.shape
+    cap = 64
+    K = ctypes.c_int(0)
+    sizes = (ctypes.c_int * (2 * cap))()
+    capi.call("pdeip_sparse_pyramid", Dm.ctypes.data, rows, cols, float(scl_factor), float(pyr_scl), cap, ctypes.addressof(K),
+              ctypes.addressof(sizes), None)
+    shapes = [(sizes[2 * k], sizes[2 * k + 1]) for k in range(K.value)]
+    out = np.empty(sum(r * c for r, c in shapes), np.float32)
+    capi.call("pdeip_sparse_pyramid", Dm.ctypes.data, rows, cols, float(scl_factor), float(pyr_scl), cap, ctypes.addressof(K),
+              ctypes.addressof(sizes), out.ctypes.data)
+    planes, at = [], 0
+    for r, c in shapes:
+        planes.append(np.asfortranarray(out[at:at + r * c].reshape(c, r).T))
+        at += r * c
+    return planes
