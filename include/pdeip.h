@@ -135,6 +135,22 @@ enum { PDEIP_PLAN_ELIN4 = 0, PDEIP_PLAN_LLIN4, PDEIP_PLAN_DISP4, PDEIP_PLAN_PDE4
 enum { PDEIP_PLAN_INFO = 11, PDEIP_PLAN_RECORD = 9 };
 int pdeip_debug_plan_sor(int model, int nrows, int ncols, int nframes, int iter, int mode, int aligned16, int has_dst, int num_cus,
                          int rb2_slots, int rbp_slots, int *info, int *records, int capacity);
+/* Diagnostic: what a line-relaxation *_dev call (solver = 2) of this shape would launch, decided as the call decides it
+ * (csrc/pdeip_alr_plan.hpp) and under the PDEIP_ALR_* knobs of the environment, without launching anything and without a HIP call:
+ * it works on a machine without a GPU.  The caller's planes are taken to be distinct, as the gateways pass them; nframes is that of
+ * the PDE models (the others have one frame); the 9-point PDE model plans one iteration whatever `iter` says, as its call runs.
+ *   info        PDEIP_PLAN_ALR_INFO ints: family (0 nothing to do, 1 k_alr_small, 2 zebra, 3 exact order, 4 scan), the launches
+ *               pdeip_last_launch_count() reports, the coefficient-transpose launches, the factor launches, whether those take both
+ *               fields at once, the iterate transposes per iteration, dynamic LDS bytes of k_alr_small and whether it needs the
+ *               opt-in, and the floats of WS_ALR, WS_ALR_T, WS_AUX1 and WS_LEX the call fetches (INT_MAX: more than that).
+ *   passes      two records of PDEIP_PLAN_ALR_PASS ints, along the columns and along the rows: kernel (1 k_alr_zebra3, 2
+ *               k_alr_zebra3_pair, 3 k_alr_lex, 4 k_alr_lex on the global line buffer, 5 k_alr_scan), first line, last line, line
+ *               length, grid x of the factor launch, colours that have a line, {first line, last line, grid x} of up to two
+ *               colours, chains per launch, launches per pass, G, dynamic LDS bytes, LDS opt-in, grid x of an exact-order or scan
+ *               launch, and the two fields in the order the pass takes them. */
+enum { PDEIP_PLAN_ALR_ELIN4 = 0, PDEIP_PLAN_ALR_LLIN4, PDEIP_PLAN_ALR_LLIN8, PDEIP_PLAN_ALR_DISP4, PDEIP_PLAN_ALR_PDE4, PDEIP_PLAN_ALR_PDE8 };
+enum { PDEIP_PLAN_ALR_INFO = 12, PDEIP_PLAN_ALR_PASS = 20 };
+int pdeip_debug_plan_alr(int model, int nrows, int ncols, int nframes, int iter, int mode, int *info, int *passes);
 /* Diagnostic: compares the fused pipeline's fast reciprocal (v_rcp_f32 + one Newton step, taken by the divisor planes of
  * opticalflowSolvers.c:111-127 when every denominator is a normal number with a normal reciprocal) with the IEEE quotient
  * 1.0f / d for EVERY such float (exponent field 1..252, both signs); counts[0] = inputs compared, counts[1] = results that differ

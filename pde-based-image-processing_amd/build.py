@@ -22,7 +22,7 @@ UNITS = {
     "pdeip_sor5.hip": ["pdeip_models.hpp", "pdeip_pointwise.hpp", "pdeip_sor_exact.hpp", "pdeip_walk_host.hpp", "pdeip_sor_rb.hpp", "pdeip_sor_rbp.hpp", "pdeip_sor_small.hpp", "pdeip_persist_host.hpp", "pdeip_sor_plan.hpp"],
     "pdeip_walk5.hip": ["pdeip_models.hpp", "pdeip_sor_exact.hpp", "pdeip_walk_host.hpp", "pdeip_sor_walk.hpp"],
     "pdeip_sor9.hip": ["pdeip_models.hpp", "pdeip_pointwise.hpp", "pdeip_sor_pde8.hpp", "pdeip_sor_pde8_persist.hpp", "pdeip_sor_exact.hpp", "pdeip_sor_rb.hpp", "pdeip_persist_host.hpp", "pdeip_sor_small.hpp", "pdeip_sor_plan.hpp"],
-    "pdeip_line.hip": ["pdeip_alr.hpp", "pdeip_models.hpp"],
+    "pdeip_line.hip": ["pdeip_alr.hpp", "pdeip_alr_plan.hpp", "pdeip_models.hpp"],
     "pdeip_stages.hip": ["pdeip_models.hpp", "pdeip_pointwise.hpp", "pdeip_flow.hpp", "pdeip_cswap.hpp", "pdeip_fas.hpp", "pdeip_sym.hpp", "pdeip_pyr.hpp",
                          "pdeip_tv.hpp"],
     "pdeip_host.hip": [],

@@ -14,14 +14,16 @@
 //               Thomas recurrences are serial along the line, so the dependency chain crosses the whole
 //               frame: there is no parallel schedule that keeps the arithmetic.  One workgroup per frame
 //               walks the lines (see below).  Bit-identical, CPU-class speed.
-//   k_alr_zebra RED_BLACK: "zebra" order -- every even line, then every odd line.  Lines of one colour
-//               only read the other colour, so they are solved concurrently, one lane per line, with the
-//               same per-line arithmetic.
+//   k_alr_zebra3 RED_BLACK: "zebra" order -- every even line, then every odd line.  Lines of one colour
+//               only read the other colour, so they are solved concurrently, with the same per-line
+//               arithmetic (k_alr_zebra3_pair: both fields of a coupled solver; k_alr_small: the whole call).
+// What a call launches is decided by plan_alr (pdeip_alr_plan.hpp), which also states the launch constants.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
 
+#include "pdeip_alr_plan.hpp"
 #include "pdeip_models.hpp"
 
 namespace pdeip {
@@ -57,7 +59,6 @@ __global__ void __launch_bounds__(256) k_alr_transpose(float *__restrict__ out, 
 }
 
 // Several planes in one launch (a coarse multigrid scale's call is bound by its number of launches): blockIdx.z = plane * F + frame.
-constexpr int ALR_TB_MAX = 16;
 struct AlrTransposeBatch {
     float *out[ALR_TB_MAX];
     const float *in[ALR_TB_MAX];
@@ -626,95 +627,6 @@ __device__ __forceinline__ Tri line_coef(const typename Mdl::Ctx &q, int l, int 
 }
 
 // ------------------------------------------------------------------------------------------------
-// Zebra order: one lane per line of the active colour.  cp/dp are scratch planes with x's layout.
-// Thomas recurrences and the lagged SOR blend as opticalflowSolvers.c:1890-1958.
-// ------------------------------------------------------------------------------------------------
-template <class Mdl, bool VERT>
-__global__ void __launch_bounds__(64) k_alr_zebra(typename Mdl::Ctx q, float *x, float *__restrict__ cp,
-                                                  float *__restrict__ dp, int nrows, int ncols, size_t frame_stride,
-                                                  int lo, int hi, int colour, float omega)
-{
-    constexpr bool vertical = VERT;
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    const int l = lo + (((lo & 1) != colour) ? 1 : 0) + 2 * t;
-    if (l > hi) return;
-    const size_t fo = (size_t)blockIdx.y * frame_stride;
-    q.shift(fo);
-    x += fo;
-    cp += fo;
-    dp += fo;
-    const int n = vertical ? nrows : ncols; // line length; line l starts at l * n in either layout
-    constexpr size_t stride = 1;
-    const size_t base = (size_t)l * n;
-    const float om1 = 1.0f - omega;
-    const bool tdiv = Mdl::SOUTH_TRUEDIV && !VERT && l == nrows - 1; // the south row of these models divides (see the model)
-
-    // The recurrences are serial, the loads are not: fetch the coefficients of ZCH steps at once so that
-    // one memory latency is paid per chunk instead of per step.
-    constexpr int ZCH = 8;
-    Tri c0 = line_coef<Mdl, VERT>(q, l, 0, nrows, ncols);
-    float cpv = c0.c / c0.b;
-    float dpv = c0.d / c0.b;
-    cp[base] = cpv;
-    dp[base] = dpv;
-    for (int k0 = 1; k0 <= n - 2; k0 += ZCH) {
-        Tri c[ZCH];
-#pragma unroll
-        for (int u = 0; u < ZCH; ++u) {
-            const int k = min(k0 + u, n - 2);
-            c[u] = line_coef<Mdl, VERT>(q, l, k, nrows, ncols);
-        }
-#pragma unroll
-        for (int u = 0; u < ZCH; ++u) {
-            const int k = k0 + u;
-            if (k <= n - 2) {
-                const float den = c[u].b - cpv * c[u].a;
-                if (tdiv) {
-                    cpv = c[u].c / den;
-                    dpv = (c[u].d - dpv * c[u].a) / den;
-                } else {
-                    const float div = 1.0f / den;
-                    cpv = c[u].c * div;
-                    dpv = (c[u].d - dpv * c[u].a) * div;
-                }
-                cp[base + k * stride] = cpv;
-                dp[base + k * stride] = dpv;
-            }
-        }
-    }
-    {
-        const int k = n - 1;
-        const Tri c = line_coef<Mdl, VERT>(q, l, k, nrows, ncols);
-        dpv = (c.d - dpv * c.a) / (c.b - cpv * c.a);
-    }
-    // back-substitution; element k+1 gets its blend once it has been used
-    float xs = dpv;
-    float old = x[base + (size_t)(n - 1) * stride];
-    for (int k0 = n - 2; k0 >= 0; k0 -= ZCH) {
-        float dpk[ZCH], cpk[ZCH], xo[ZCH];
-#pragma unroll
-        for (int u = 0; u < ZCH; ++u) {
-            const size_t pos = base + (size_t)max(k0 - u, 0) * stride;
-            dpk[u] = dp[pos];
-            cpk[u] = cp[pos];
-            xo[u] = x[pos];
-        }
-#pragma unroll
-        for (int u = 0; u < ZCH; ++u) {
-            const int k = k0 - u;
-            if (k >= 0) {
-                const size_t pos = base + (size_t)k * stride;
-                const float xk = dpk[u] - cpk[u] * xs;
-                x[pos + stride] = omega * xs + om1 * old;
-                old = xo[u];
-                xs = xk;
-            }
-        }
-    }
-    x[base] = omega * xs + om1 * old;
-}
-
-// ------------------------------------------------------------------------------------------------
 // Zebra order on a small frame: the whole call in ONE launch, one workgroup per frame.
 //
 // On the coarse scales of the drivers' pyramids a zebra call is ~45 launches (coefficient transposes, factor passes, per
@@ -728,10 +640,8 @@ __global__ void __launch_bounds__(64) k_alr_zebra(typename Mdl::Ctx q, float *x,
 //     everywhere -- into LDS next to the line's factors and old x, in parallel over lines AND elements; one lane per line
 //     runs the two short recurrences out of LDS (three dependent instructions per element going down, two coming back);
 //     every thread copies the blended lines back to the plane.
-// Bit-identical to k_alr_zebra3 / k_alr_zebra.  Frames whose largest colour pass fits 150 KB of LDS.
+// Bit-identical to k_alr_zebra3.  Frames whose largest colour pass fits 150 KB of LDS.
 // ------------------------------------------------------------------------------------------------
-constexpr int ALR_SMALL_THREADS = 1024;
-constexpr int ALR_SMALL_MAXTR = 24;
 template <class Mdl> struct AlrSmallArgs {
     typename Mdl::Ctx q[2], qt[2];
     float *x[2], *xt[2];
@@ -744,22 +654,9 @@ template <class Mdl> struct AlrSmallArgs {
 };
 
 // floats the row part of the LDS image takes (the old / new x part follows it)
-__host__ __device__ inline size_t alr_small_lds_bytes_dev(int nrows, int ncols, bool interior_lines)
+__host__ __device__ inline size_t alr_small_row_floats(int nrows, int ncols, bool interior_lines)
 {
-    const int lo = interior_lines ? 1 : 0;
-    const size_t col_lines = (size_t)(ncols - 2 * lo + 1) / 2, row_lines = (size_t)(nrows - 2 * lo + 1) / 2;
-    const size_t a = col_lines * (size_t)(nrows | 1), b = row_lines * (size_t)(ncols | 1);
-    return (a > b ? a : b) * 4;
-}
-// LDS per colour pass: a row (a, divisor, cp, d) and the old / new x of every element of the colour's lines; lines padded to an
-// odd number of rows so that the lanes of the recurrence stage (one per line) hit different banks
-__host__ __device__ inline int alr_small_stride(int n) { return n | 1; }
-inline size_t alr_small_lds_bytes(int nrows, int ncols, bool interior_lines)
-{
-    const int lo = interior_lines ? 1 : 0;
-    const size_t col_lines = (size_t)(ncols - 2 * lo + 1) / 2, row_lines = (size_t)(nrows - 2 * lo + 1) / 2;
-    const size_t a = col_lines * alr_small_stride(nrows), b = row_lines * alr_small_stride(ncols);
-    return (a > b ? a : b) * (sizeof(float4) + sizeof(float));
+    return alr_small_elems(nrows, ncols, interior_lines) * 4;
 }
 
 // FACTOR = true: once per call and direction, the coefficient-only recurrence of every line of one colour:
@@ -768,7 +665,7 @@ inline size_t alr_small_lds_bytes(int nrows, int ncols, bool interior_lines)
 // FACTOR = false: one relaxation of the lines of one colour with those planes:
 //   dp[0] = d / divisor[0];  middle: dp = (d - dp' a) * divisor (dividing south row: / divisor);  last: dp = (d - dp' a) / divisor;
 //   back-substitution x[k] = dp[k] - cp[k] x[k+1] with the lagged SOR blend (opticalflowSolvers.c:1890-1958).
-// The same statements as k_alr_zebra with 1/den hoisted out of the iteration, as k_alr_zebra3 does.
+// The same statements as k_alr_zebra3: 1/den hoisted out of the iteration.
 template <class Mdl, bool VERT, bool FACTOR>
 __device__ __forceinline__ void alr_small_pass(const typename Mdl::Ctx &q, float *x, float *cpP, float *dvP, float4 *T, float *X, int nrows,
                                                int ncols, int colour, float omega)
@@ -895,7 +792,7 @@ __global__ void __launch_bounds__(ALR_SMALL_THREADS) k_alr_small(AlrSmallArgs<Md
     const int tid = threadIdx.x, nrows = A.nrows, ncols = A.ncols, n = nrows * ncols;
     const size_t fo = (size_t)blockIdx.x * A.fs;
     float4 *const T = alr_small_lds;
-    float *const X = reinterpret_cast<float *>(alr_small_lds) + alr_small_lds_bytes_dev(nrows, ncols, Mdl::INTERIOR_LINES);
+    float *const X = reinterpret_cast<float *>(alr_small_lds) + alr_small_row_floats(nrows, ncols, Mdl::INTERIOR_LINES);
     // two fields at most; named copies rather than arrays indexed at run time (those would live in scratch memory)
     typename Mdl::Ctx q0 = A.q[0], q1 = A.q[1], qt0 = A.qt[0], qt1 = A.qt[1];
     q0.shift(fo);
@@ -959,8 +856,8 @@ __global__ void __launch_bounds__(ALR_SMALL_THREADS) k_alr_small(AlrSmallArgs<Md
 // (lane = line, runs the recurrences) fed by seven MOVER waves.
 //
 // A lane that walks its own line makes every load instruction touch 64 cache lines for 256 useful
-// bytes, and one wave can keep only ~63 such loads in flight: k_alr_zebra is bound by that, not by the
-// recurrences.  Here the movers fetch the operands of [16 lines x 32 elements] tiles with 16-byte loads
+// bytes, and one wave can keep only ~63 such loads in flight: a kernel of one lane per line is bound by
+// that, not by the recurrences.  Here the movers fetch the operands of [16 lines x 32 elements] tiles with 16-byte loads
 // (eight lanes cover 128 contiguous bytes of a line), turn them into (a,b,c,d) rows with the same
 // Model::math as everywhere else and park them in LDS; the solver reads its line's rows back and leaves
 // cp,dp in their place, which the movers write out with 16-byte stores during the next round.
@@ -968,15 +865,11 @@ __global__ void __launch_bounds__(ALR_SMALL_THREADS) k_alr_small(AlrSmallArgs<Md
 // Rounds of 7 tiles are double-buffered; one barrier per round is the only synchronisation.  Only 16
 // lines per workgroup because the frame has only ~1000-2000 lines per colour: the recurrences cost the
 // same however many lanes run them, but 120 workgroups pull operands through 120 CUs' memory paths
-// instead of 30.  Arithmetic and operand order are those of k_alr_zebra (bit-identical).
+// instead of 30.  Arithmetic and operand order are those of alr_small_pass (bit-identical).
 // ------------------------------------------------------------------------------------------------
-constexpr int ZB_NM = 7;                        // mover waves = tiles per round
-constexpr int ZB_LW = 8;                        // lines per workgroup
-constexpr int ZB_TE = 32;                       // elements per tile
 constexpr int ZB_GP = ZB_TE / 4;                // 4-element groups per line of a tile
 constexpr int ZB_LP = 64 / ZB_GP;               // lines one mover pass covers
 constexpr int ZB_NP = ZB_LW / ZB_LP;            // mover passes per tile
-constexpr int ZB_THREADS = 64 * (1 + ZB_NM);
 static_assert(ZB_NP * ZB_LP == ZB_LW, "zebra tile geometry");
 
 __device__ __forceinline__ void alr_st4(float *p, float a, float b, float c, float d)
@@ -1007,11 +900,8 @@ enum { ZB_FACTOR = 1, ZB_APPLY = 2 };
 //     loop trip;
 // which leaves 4 instructions per element going down (3 of them the dependent mul-sub-mul) and 2.75 coming
 // back.  Arithmetic, operand order and results are those of k_alr_zebra2 (bit-identical).
+// The tile geometry (Z3_LSF, Z3_TILE, Z3_LDS_BYTES) is stated in pdeip_alr_plan.hpp.
 // ------------------------------------------------------------------------------------------------
-constexpr int Z3_LSF = 3 * ZB_TE + 4;              // floats per line of a tile; +4 keeps the 16 lines' b128 reads on distinct banks
-constexpr int Z3_TILE = ZB_LW * Z3_LSF;            // floats per tile
-constexpr size_t Z3_LDS_BYTES = (size_t)2 * ZB_NM * Z3_TILE * sizeof(float);
-
 template <class Mdl, bool VERT, int MODE>
 __device__ __forceinline__ void alr_zebra3_body(typename Mdl::Ctx q, float *x, float *__restrict__ cp, float *__restrict__ dv,
                                                 float *__restrict__ dp, int nrows, int ncols, size_t frame_stride, int first, int lastc,
@@ -1415,8 +1305,6 @@ __global__ void __launch_bounds__(ZB_THREADS) k_alr_factor_pair(typename Mdl::Ct
 // recurrences.  For the two-field solvers the second field's pass runs one line behind the first
 // field's in the same workgroup (it only needs the first field's finished line l and its own l-1).
 // ------------------------------------------------------------------------------------------------
-constexpr int ALR_LEX_THREADS = 1024;
-
 template <class Mdl> struct AlrChain {
     typename Mdl::Ctx q;
     float *x;            // the plane this chain solves (q reads it too)
@@ -1616,11 +1504,8 @@ __global__ void __launch_bounds__(ALR_LEX_THREADS) k_alr_lex(AlrChains<Mdl, NCH>
 // on the ALR_SCAN_* constants and G only.  (k_alr_lex's idle waves touch the next line's operands ahead of its build; here every
 // wave is busy, and the same loads issued between the barriers cost more than they saved: 11.8 against 9.5 us per 4K line step.)
 // ------------------------------------------------------------------------------------------------
-constexpr int ALR_SCAN_THREADS = ALR_LEX_THREADS;
 constexpr int ALR_SCAN_LANES = 64;
 constexpr int ALR_SCAN_WAVES = ALR_SCAN_THREADS / ALR_SCAN_LANES;
-constexpr int ALR_SCAN_VEC = 4;  // elements per group: one coef4
-constexpr int ALR_SCAN_MAXG = 3; // groups per lane at most: lines of up to 12 288 elements (6 144 for each of two coupled fields)
 
 struct AlrAff { // y -> m y + t
     float m, t;

@@ -1,7 +1,7 @@
 """PDEIP_MODE_LINE_SCAN (line relaxation in the reference's line order, a line's two recurrences as scans): the cases, the
 bounds and the runners that tests/test_line_scan_tolerance.py (reference side, no GPU) and tests/test_gpu_line_scan.py share.
 
-The constants restate pdeip_alr.hpp (ALR_SCAN_*) and the dispatch of alr_lex_pass / alr_scan_pass (pdeip_line.hip), as
+The constants restate pdeip_alr.hpp (ALR_SCAN_*) and the decision of plan_alr (pdeip_alr_plan.hpp), as
 seam_model.py restates the strip kernels': a lane of k_alr_scan holds VEC * G consecutive elements, G = 1, 2 or 3 chosen from the
 line length and the number of coupled fields alone, 64 lanes scan by DPP in rows of 16, the wave totals cross the workgroup through
 LDS; the two fields of a coupled model take half of the 1 024 threads each.
@@ -33,7 +33,7 @@ def scan_groups(model, n):
 
 
 def scan_runs(model, nrows, ncols):
-    """Does a LINE_SCAN call of this frame run k_alr_scan, or k_alr_lex in both directions (run_alr decides per call)?"""
+    """Does a LINE_SCAN call of this frame run k_alr_scan, or k_alr_lex in both directions (plan_alr decides per call)?"""
     return sm.ALR[model][0] * 16 * max(nrows, ncols) <= LEX_LDS_BYTES
 
 

@@ -23,8 +23,8 @@ RB_HALO = 4                  # rb_march2 starts three columns west of its strip 
 P8_OWN_ROWS2 = 240           # pdeip_sor_pde8.hpp, the two-sweep four-colour kernel (the one-sweep kernel owns RB_OWN_ROWS)
 RB_WAVES_PER_BLOCK = 4       # units per workgroup of k_sor_rb / k_pde8_colour*
 PIPE_MIN_PIXELS = 1 << 21    # single-field models enter the pipeline from here on (pdeip_sor5.hip)
-ALR_SMALL_MAX_PIXELS = 6144  # k_alr_small takes every frame up to here (pdeip_line.hip)
-ALR_TB_MAX = 16              # planes per transpose launch (pdeip_alr.hpp)
+ALR_SMALL_MAX_PIXELS = 6144  # k_alr_small takes every frame up to here (pdeip_alr_plan.hpp)
+ALR_TB_MAX = 16              # planes per transpose launch (pdeip_alr_plan.hpp)
 ALR_SMALL_MAXTR = 24
 
 # model -> (NIT iterate fields, NRO read-only fields, NCF coefficient planes)   (pdeip_models.hpp)
@@ -166,7 +166,7 @@ def geometry(kernel, model, nrows, ncols, tj, aligned=True):
     return Geometry(tiles, nrows - (tiles - 1) * own, strips, last, nrows % 4 == 0 and aligned, last <= halo, grid)
 
 
-# ---- run_alr (pdeip_line.hip) -----------------------------------------------------------------------------------------
+# ---- plan_alr (pdeip_alr_plan.hpp), restated; tests/test_alr_plan.py compares the two on the CPU ---------------------
 ALR = {  # model -> (fields, distinct planes that are not the iterate, interior lines only)
     "elin4": (2, 9, False), "llin4": (2, 11, False), "llin8": (2, 15, False), "disp4": (1, 7, False), "pde4": (1, 6, False), "pde8": (1, 10, True)}
 
@@ -592,7 +592,7 @@ def exact_launches(model, nrows, ncols, it, form):
 
 
 def alr_exact_launches(model, nrows, ncols, it):
-    """Exact order: launches of a line-relaxation call (run_alr, alr_lex_pass).  The coefficient planes transposed (one launch per
+    """Exact order: launches of a line-relaxation call (plan_alr).  The coefficient planes transposed (one launch per
     16), the factor planes of both directions (2), then per iteration a pass along the columns, the iterate transposed, a pass
     along the rows, the iterate transposed back.  A pass of a coupled model walks both chains in one launch (k_alr_lex<2>) where two
     lines of float4 fit the 160 KiB of LDS, and one chain per launch otherwise -- which is how a call shows the form it ran."""

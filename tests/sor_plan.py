@@ -6,7 +6,7 @@ import os
 from collections import namedtuple
 
 KNOBS = ("PDEIP_RB_SMALL", "PDEIP_RB_PIPE", "PDEIP_RBP_TJ", "PDEIP_RB_TJ", "PDEIP_RBP_SERPENTINE", "PDEIP_ALR_SMALL", "PDEIP_ALR_PAIR",
-         "PDEIP_EXACT_PERSIST", "PDEIP_EXACT_WALK", "PDEIP_PDE8_PERSIST")  # the last three: the exact-order forms (test_gpu_range.py)
+         "PDEIP_ALR_SCAN", "PDEIP_EXACT_PERSIST", "PDEIP_EXACT_WALK", "PDEIP_PDE8_PERSIST")  # the last three: the exact-order forms (test_gpu_range.py)
 
 
 @contextlib.contextmanager

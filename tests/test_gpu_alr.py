@@ -2,7 +2,7 @@
 the C-ABI against the CPU oracle.  Bar: bit-exact.
 
 EXACT_ORDER mode = the reference's line order (serial walk, k_alr_lex); RED_BLACK mode = zebra order
-(k_alr_zebra) against the oracle's zebra order.
+(k_alr_zebra3, k_alr_zebra3_pair and, on small frames, k_alr_small) against the oracle's zebra order.
 """
 import numpy as np
 import pytest

@@ -14,8 +14,10 @@ import importlib
 
 import pytest
 
+import line_scan_cases as lsc
 import problems as pb
 import seam_model as sm
+from alr_plan import plan_alr
 from sor_plan import knobs, plan_sor, point_case_knobs
 
 pytestmark = pytest.mark.gpu
@@ -240,3 +242,51 @@ def test_plan_lists_the_launches_of_an_exact_order_call(pdeip, oracle, persist):
         assert pb.bit_equal(g, w), pb.describe_mismatch(g, w)
     assert plan.form == ("persist" if persist is None else "front")
     assert len(plan.launches) == launches == sm.exact_launches("elin4", 5, 7, 2, plan.form)
+
+
+OFF = dict(PDEIP_ALR_SMALL=0)
+# The smallest frame at which each path of a line-relaxation plan exists (iter = 2 unless the line is long):
+#             model    rows   cols it mode  knobs                        family   passes along the columns / rows: (kernel, chains per launch, G)
+ALR_PLAN_CASES = [
+    ("elin4", 3,     3,    2, 1, {},                          "small", None),                                                   # one launch
+    ("elin4", 3,     3,    2, 1, OFF,                         "zebra", (("k_alr_zebra3_pair", 2, 0), ("k_alr_zebra3_pair", 2, 0))),
+    ("elin4", 3,     3,    2, 1, dict(OFF, PDEIP_ALR_PAIR=0), "zebra", (("k_alr_zebra3", 1, 0), ("k_alr_zebra3", 1, 0))),        # per field
+    ("pde8",  3,     3,    2, 1, OFF,                         "zebra", (("k_alr_zebra3", 1, 0), ("k_alr_zebra3", 1, 0))),        # one colour per direction
+    ("disp4", 3,     2049, 2, 1, {},                          "zebra", (("k_alr_zebra3", 1, 0), ("k_alr_zebra3", 1, 0))),        # past the pixel gate
+    ("elin4", 3,     3,    2, 0, {},                          "exact", (("k_alr_lex", 2, 0), ("k_alr_lex", 2, 0))),              # two chains in LDS
+    ("elin4", 5121,  3,    1, 0, {},                          "exact", (("k_alr_lex", 1, 0), ("k_alr_lex", 2, 0))),              # one chain per launch one way
+    ("pde4",  10241, 3,    1, 0, {},                          "exact", (("k_alr_lex global", 1, 0), ("k_alr_lex", 1, 0))),       # the global line buffer
+    ("elin4", 2049,  3,    2, 2, {},                          "scan",  (("k_alr_scan", 2, 2), ("k_alr_scan", 2, 1))),
+    ("disp4", 8193,  3,    2, 2, {},                          "scan",  (("k_alr_scan", 1, 3), ("k_alr_scan", 1, 1))),
+    ("elin4", 5121,  3,    2, 2, {},                          "exact", (("k_alr_lex", 1, 0), ("k_alr_lex", 2, 0))),              # the scan's fallback
+]
+
+
+@pytest.mark.parametrize("model,nrows,ncols,it,mode,env,family,passes", ALR_PLAN_CASES,
+                         ids=["%s-%dx%d-mode%d-%s%s" % (c[0], c[1], c[2], c[4], c[6], "".join("-%s=%s" % kv for kv in c[5].items())) for c in ALR_PLAN_CASES])
+def test_plan_lists_the_launches_of_a_line_relaxation_call(pdeip, oracle, model, nrows, ncols, it, mode, env, family, passes):
+    """pdeip_debug_plan_alr under the call's knobs names the family and as many launches as the call made.  The call's values: the
+    oracle's bits in its zebra order (mode 1) and in the reference's line order (mode 0, and mode 2 where the plan falls back to the
+    exact-order kernels); where the plan scans, within test_gpu_line_scan's bounds of the reference's line order."""
+    c = lsc.Case(model, nrows, ncols, 1, lsc.OMEGA[model], (it,), True)
+    p = lsc.problem(c)
+    want = lsc.as_tuple(getattr(oracle, lsc.MODELS[model][0])(*p.values(), it, c.omega, solver=2, order=1 if mode == 1 else 0))[:len(lsc.MODELS[model][1])]
+    pdeip.mex_api.set_mode(mode)
+    try:
+        with knobs(**env):
+            got = lsc.run_product(pdeip.mex_api, c, p, it)
+            launches = pdeip.capi.load().pdeip_last_launch_count()
+            plan = plan_alr(pdeip.capi, model, nrows, ncols, 1, it, mode)
+    finally:
+        pdeip.mex_api.set_mode(pdeip.MODE_EXACT_ORDER)
+    assert plan.family == family and plan.nlaunch == launches, (plan, launches)
+    if passes is not None:
+        assert tuple((q.kernel, q.chains, q.G) for q in (plan.cols, plan.rows)) == passes
+    if family == "scan":
+        rms_bound, max_bound = lsc.bounds(c)
+        for k, (rms, mx) in enumerate(lsc.differences(got, want)):
+            print("%s plane %d: rms %.3g max %.3g" % (lsc.case_id(c), k, rms, mx))
+            assert rms <= lsc.RMS_BOUND and rms <= rms_bound and (max_bound is None or mx <= max_bound), (k, rms, mx)
+    else:
+        for k, (g, w) in enumerate(zip(got, want)):
+            assert pb.bit_equal(g, w), "plane %d: %s" % (k, pb.describe_mismatch(g, w))
