@@ -671,6 +671,23 @@ int pdeip_gac(const float *Iin, int nrows, int ncols, int channels, const float 
 /* The same on device pointers, asynchronous on `stream` (no host read-back inside: graph-capturable). */
 int pdeip_gac_dev(void *stream, const float *Iin, int nrows, int ncols, int channels, const float *PHIin, int model,
                   const pdeip_gac_params *prm, float *PHIout);
+/* The stages of the driver that come before its loop, on device pointers, asynchronous on `stream`, no host read-back (graph-
+ * capturable); pdeip_gac_dev runs through these two, so a caller of either runs the driver's own code.
+ * pdeip_select_kth_dev: *out = the k-th smallest (1-based) of x[0..n), what MATLAB's Y = sort(x); Y(k) gives: NaN sort last (k may
+ * point into them: the result is then a NaN), -Inf and +Inf are ordinary values.  The key orders -0.0 below +0.0, which sort()
+ * leaves in the order they came: where the k-th element is a zero, only its value is defined, not its sign.  By four passes over
+ * x, one per 8-bit digit of an order-preserving key (a 256-bin histogram on at most 1024 workgroups, then the digit that holds
+ * the rank); the state is cleared at the start of every call, so nothing survives from one call to the next.  Nine launches.
+ * Refused with PDEIP_ERR_ARG before any HIP call: a NULL pointer, n < 1 or > 2^31-1, k < 1, k > n.
+ * pdeip_gac_stopping_dev (GAC_v10a.m:57-75): Igrad_out = max_c(Idx).^2 + max_c(Idy).^2 of the channels of I smoothed with the 7x7
+ * Gaussian (sigma 2.5), the derivatives [-1 0 1]*0.5 with a replicated border and max() over the channels ignoring NaN (the first of
+ * equal values kept); *lambda_out = the element of rank round(0.7*N) of Igrad_out when lambda < 0, N = nrows*ncols and round() taken
+ * of the double product as MATLAB does (N = 45: 0.7*45 = 31.499999999999996, rank 31, not 32), otherwise lambda rounded to single
+ * (a NaN included); g_out = 1 ./ (1 + Igrad_out ./ *lambda_out) in single with true divisions.  I: [nrows x ncols x channels];
+ * Igrad_out, g_out: [nrows x ncols], not aliasing I or each other; lambda_out: one device float.  Refusals as pdeip_gac_dev's. */
+int pdeip_select_kth_dev(void *stream, const float *x, long long n, long long k, float *out);
+int pdeip_gac_stopping_dev(void *stream, const float *I, int nrows, int ncols, int channels, double lambda, float *Igrad_out,
+                           float *g_out, float *lambda_out);
 
 /* ---- nonlinear diffusion (csrc/pdeip_diffusion.hip) -----------------------------------------------------------------------
  * Iout = Diffusion4_v10(I_in, 'alpha', alpha, 'outer_iter', outer_iter) (matlab/diffusion/Diffusion4_v10.m) before its uint8

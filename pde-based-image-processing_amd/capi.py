@@ -127,6 +127,8 @@ SIGNATURES = {
     "pdeip_reinit_dev": [_P, _P, _I, _I, _I, _F, _P],
     "pdeip_gac": [_P, _I, _I, _I, _P, _I, _P, _P],
     "pdeip_gac_dev": [_P, _P, _I, _I, _I, _P, _I, _P, _P],
+    "pdeip_select_kth_dev": [_P, _P, ctypes.c_longlong, ctypes.c_longlong, _P],
+    "pdeip_gac_stopping_dev": [_P, _P, _I, _I, _I, ctypes.c_double, _P, _P, _P],
     "pdeip_cv_solver": [_P, _P, _P, _P, _I, _I, _I, _F, _F, _P],
     "pdeip_cv_terms": [_P, _I, _I, _I, _F, _F, _F, _P, _P],
     "pdeip_cv_solver_dev": [_P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P],

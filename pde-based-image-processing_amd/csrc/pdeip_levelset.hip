@@ -4,6 +4,8 @@
 //   PHI_out = Reinit(PHI, T)                                  mex/source/Reinit.c       -> reinit         pdeip_reinit(_dev)
 //   PHI_out = CV_solver_2d(PHI, D, DH, GradNorm, tau, nu)     mex/source/CV_solver_2d.c -> CV_AOSOMP_4_2d pdeip_cv_solver(_dev)
 //   [DH, gradPHI] of the segmentation drivers                                                            pdeip_cv_terms(_dev)
+//   PHIout = GAC_v10a / GAC_v10b(Iin, PHIin, ...)             matlab/active_contour/GAC_v10{a,b}.m      pdeip_gac(_dev)
+//   sort(x)(k) and [Igrad, lambda, g] of those drivers: the stages before their loop                     pdeip_select_kth_dev, pdeip_gac_stopping_dev
 //
 // Kernels: csrc/pdeip_levelset.hpp, csrc/pdeip_cv.hpp.  AOS has one order, so pdeip_set_mode does not apply.  Multi-frame inputs are planes
 // solved independently, as in the reference.  Lines of any length are accepted (the reference stops at MAX_BUF_SIZE = 2048).
@@ -176,14 +178,75 @@ GacPrm gac_resolve(const pdeip_gac_params *u)
 
 } // namespace
 
+// The k-th smallest (1-based) of x[0..n), NaN last: k_sel_init, then per 8-bit digit of the order-preserving key (most significant first)
+// one k_sel_hist over x and one k_sel_pick.  Nine launches; the state lives in its own workspace slot and every call clears it first.
+extern "C" int pdeip_select_kth_dev(void *stream, const float *x, long long n, long long k, float *out)
+{
+    const char *who = "pdeip_select_kth_dev";
+    NONNULL(who, x); NONNULL(who, out);
+    if (n < 1 || n > 0x7fffffffLL) return set_err(PDEIP_ERR_ARG, "%s: n must be in 1 .. 2^31-1 (got %lld)", who, n);
+    if (k < 1 || k > n) return set_err(PDEIP_ERR_ARG, "%s: k must be in 1 .. n (got %lld of %lld)", who, k, n);
+    float *ws = nullptr;
+    RC(ws_get(WS_SELECT, sizeof(Select), &ws));
+    Select *sel = reinterpret_cast<Select *>(ws);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(k_sel_init, dim3(1), dim3(256), 0, s, sel, (unsigned)k);
+    const unsigned blocks = (unsigned)std::min<size_t>(((size_t)n + 255) / 256, 1024);
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        hipLaunchKernelGGL(k_sel_hist, dim3(blocks), dim3(256), 0, s, sel, x, (size_t)n, shift);
+        hipLaunchKernelGGL(k_sel_pick, dim3(1), dim3(64), 0, s, sel, shift, out);
+    }
+    HIPCHK(hipGetLastError());
+    tls.last_launches = 9;
+    return PDEIP_OK;
+}
+
+namespace {
+int check_gac_dims(const char *who, int nrows, int ncols, int channels)
+{
+    if (nrows < 3 || ncols < 3) return set_err(PDEIP_ERR_ARG, "%s: image must be at least 3x3 (got %dx%d)", who, nrows, ncols);
+    if (channels < 1) return set_err(PDEIP_ERR_ARG, "%s: number of channels must be >= 1 (got %d)", who, channels);
+    if ((long long)nrows * ncols * (channels + 9) > 0x7fffffffLL) return set_err(PDEIP_ERR_ARG, "%s: image too large", who);
+    return PDEIP_OK;
+}
+} // namespace
+
+// Igrad, lambda and g of the drivers (GAC_v10a.m:57-75): the smoothing, k_gac_igrad, the selection when lambda < 0, k_gac_g.
+extern "C" int pdeip_gac_stopping_dev(void *stream, const float *I, int nrows, int ncols, int channels, double lambda, float *Igrad_out,
+                                      float *g_out, float *lambda_out)
+{
+    const char *who = "pdeip_gac_stopping_dev";
+    NONNULL(who, I); NONNULL(who, Igrad_out); NONNULL(who, g_out); NONNULL(who, lambda_out);
+    RC(check_gac_dims(who, nrows, ncols, channels));
+    if (Igrad_out == I || g_out == I || Igrad_out == g_out) return set_err(PDEIP_ERR_ARG, "%s: Igrad_out and g_out must not alias I or each other", who);
+    const size_t n = (size_t)nrows * ncols, pn = pad4(n);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    float *Ism = nullptr;
+    RC(ws_get(WS_GAC, pn * (size_t)channels * sizeof(float), &Ism));
+    const std::vector<double> G = gaussian_mask(7, 2.5);
+    RC(pdeip_pyr_smooth_dev(s, I, nrows, ncols, channels, G.data(), 7, Ism));
+    hipLaunchKernelGGL(k_gac_igrad, pixel_grid(nrows, ncols, 1), dim3(256), 0, s, Ism, Igrad_out, nrows, ncols, channels);
+    HIPCHK(hipGetLastError());
+    int launches = 2;
+    const float *lam_dev = nullptr;
+    if (lambda < 0.0) {
+        const double kd = std::round(0.7 * (double)n); // MATLAB round: half away from zero; 1-based rank
+        RC(pdeip_select_kth_dev(s, Igrad_out, (long long)n, kd < 1.0 ? 1LL : (long long)kd, lambda_out));
+        launches += tls.last_launches;
+        lam_dev = lambda_out;
+    }
+    hipLaunchKernelGGL(k_gac_g, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, Igrad_out, g_out, n, lam_dev, (float)lambda, lambda_out);
+    HIPCHK(hipGetLastError());
+    tls.last_launches = launches + 1;
+    return PDEIP_OK;
+}
+
 extern "C" int pdeip_gac_dev(void *stream, const float *Iin, int nrows, int ncols, int channels, const float *PHIin, int model,
                              const pdeip_gac_params *prm, float *PHIout)
 {
     const char *who = "pdeip_gac_dev";
     NONNULL(who, Iin); NONNULL(who, PHIin); NONNULL(who, PHIout);
-    if (nrows < 3 || ncols < 3) return set_err(PDEIP_ERR_ARG, "%s: image must be at least 3x3 (got %dx%d)", who, nrows, ncols);
-    if (channels < 1) return set_err(PDEIP_ERR_ARG, "%s: number of channels must be >= 1 (got %d)", who, channels);
-    if ((long long)nrows * ncols * (channels + 9) > 0x7fffffffLL) return set_err(PDEIP_ERR_ARG, "%s: image too large", who);
+    RC(check_gac_dims(who, nrows, ncols, channels));
     if (model != PDEIP_GAC_A && model != PDEIP_GAC_B) return set_err(PDEIP_ERR_ARG, "%s: model must be PDEIP_GAC_A or PDEIP_GAC_B", who);
     const GacPrm p = gac_resolve(prm);
     if (!(p.iter < 2147483647.0)) return set_err(PDEIP_ERR_ARG, "%s: ITER = %g is too large", who, p.iter);
@@ -192,37 +255,16 @@ extern "C" int pdeip_gac_dev(void *stream, const float *Iin, int nrows, int ncol
     hipStream_t s = static_cast<hipStream_t>(stream);
 
     float *ws = nullptr;
-    const size_t sel_floats = (sizeof(Select) + 3) / 4 + 8; // lambda (4 floats, keeps the state 16-byte aligned) + the state
-    RC(ws_get(WS_DRIVER, (pn * ((size_t)channels + 9) + sel_floats) * sizeof(float), &ws));
-    float *Ism = ws, *Igrad = Ism + pn * channels, *g = Igrad + pn, *gdx = g + pn, *gdy = gdx + pn, *P0 = gdy + pn, *P1 = P0 + pn;
+    RC(ws_get(WS_DRIVER, (pn * 9 + 4) * sizeof(float), &ws)); // the smoothed channels and the selection state: pdeip_gac_stopping_dev's
+    float *Igrad = ws, *g = Igrad + pn, *gdx = g + pn, *gdy = gdx + pn, *P0 = gdy + pn, *P1 = P0 + pn;
     float *DATA = P1 + pn, *gradPHI = DATA + pn, *Diff = gradPHI + pn, *lam = Diff + pn;
-    Select *sel = reinterpret_cast<Select *>(lam + 4);
     int launches = 0;
 
     RC(pdeip_reinit_dev(s, PHIin, nrows, ncols, 1, 10.0f, P0)); // Reinit(single(PHIin), single(10)): 40 steps
     launches += tls.last_launches;
-    const std::vector<double> G = gaussian_mask(7, 2.5);
-    RC(pdeip_pyr_smooth_dev(s, Iin, nrows, ncols, channels, G.data(), 7, Ism));
+    RC(pdeip_gac_stopping_dev(s, Iin, nrows, ncols, channels, p.lambda, Igrad, g, lam));
+    launches += tls.last_launches;
     const dim3 grid = pixel_grid(nrows, ncols, 1), blk(256);
-    hipLaunchKernelGGL(k_gac_igrad, grid, blk, 0, s, Ism, Igrad, nrows, ncols, channels);
-    HIPCHK(hipGetLastError());
-    launches += 2;
-    const float *lam_dev = nullptr;
-    if (p.lambda < 0.0) {
-        const double kd = std::round(0.7 * (double)n); // MATLAB round: half away from zero; 1-based rank
-        const unsigned k = kd < 1.0 ? 1u : (unsigned)kd;
-        hipLaunchKernelGGL(k_sel_init, dim3(1), dim3(256), 0, s, sel, k);
-        const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 1024);
-        for (int shift = 24; shift >= 0; shift -= 8) {
-            hipLaunchKernelGGL(k_sel_hist, dim3(blocks), dim3(256), 0, s, sel, Igrad, n, shift);
-            hipLaunchKernelGGL(k_sel_pick, dim3(1), dim3(64), 0, s, sel, shift, lam);
-        }
-        HIPCHK(hipGetLastError());
-        launches += 9;
-        lam_dev = lam;
-    }
-    hipLaunchKernelGGL(k_gac_g, dim3((unsigned)((n + 255) / 256)), blk, 0, s, Igrad, g, n, lam_dev, (float)p.lambda);
-    launches++;
     if (model == PDEIP_GAC_B) {
         hipLaunchKernelGGL(k_gac_gd, grid, blk, 0, s, g, gdx, gdy, nrows, ncols);
         launches++;

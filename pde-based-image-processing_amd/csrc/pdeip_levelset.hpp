@@ -309,12 +309,14 @@ __global__ void k_sel_pick(Select *st, int shift, float *lambda)
     if (shift == 0) *lambda = sel_unkey(st->prefix);
 }
 
-// g = 1./(1 + Igrad./lambda) (:70-75); lambda: the selected value (device) or the caller's (lam_dev == nullptr)
-__global__ void k_gac_g(const float *__restrict__ Igrad, float *__restrict__ g, size_t n, const float *__restrict__ lam_dev, float lam)
+// g = 1./(1 + Igrad./lambda) (:70-75); lambda: the selected value (device) or the caller's (lam_dev == nullptr), which is then
+// also written to *lam_out
+__global__ void k_gac_g(const float *__restrict__ Igrad, float *__restrict__ g, size_t n, const float *lam_dev, float lam, float *lam_out)
 {
     const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n) return;
     const float l = lam_dev ? *lam_dev : lam;
+    if (p == 0 && lam_dev == nullptr) *lam_out = l;
     const float t = Igrad[p] / l;
     g[p] = 1.0f / (1.0f + t);
 }

@@ -208,6 +208,20 @@ def reinit(PHI, T, out):
     capi.call("pdeip_reinit_dev", _stream(), PHI.data_ptr(), nrows, ncols, F, float(T), out.data_ptr())
 
 
+def select_kth(x, k, out):
+    """out[0] = the k-th smallest (1-based) element of x (any shape, all of it), NaN last: sort(x(:))(k).  out: one float32."""
+    _chk(x, out)
+    capi.call("pdeip_select_kth_dev", _stream(), x.data_ptr(), int(x.numel()), int(k), out.data_ptr())
+
+
+def gac_stopping(I, lam, Igrad_out, g_out, lam_out):
+    """Igrad, g and lambda of the GAC drivers (GAC_v10a.m:57-75) from the image planes I [(C,) ncols, nrows]; lam < 0 selects
+    lambda as the drivers do.  Igrad_out, g_out: planes [ncols, nrows]; lam_out: one float32."""
+    _chk(I, Igrad_out, g_out, lam_out)
+    nrows, ncols, C = _dims(I)
+    capi.call("pdeip_gac_stopping_dev", _stream(), I.data_ptr(), nrows, ncols, C, float(lam), *_p(Igrad_out, g_out, lam_out))
+
+
 def cv_solver(PHI, D, DH, GradNorm, tau, nu, out):
     """out = one AOS step of the Chan-Vese model (CV_solver_2d); `out` must not alias an input."""
     _chk(PHI, D, DH, GradNorm, out)

@@ -17,7 +17,8 @@ from test_mex_stubs import MOCK_DIR, ROOT, call
 LS_DIR = os.path.join(ROOT, "pde-based-image-processing_amd", "mex", "levelset")
 BUILD_DIR = os.path.join(MOCK_DIR, "_build")
 LS_STUBS = ["AC_solver_2d", "Reinit", "GAC_v10a_gpu", "GAC_v10b_gpu"]
-ENTRIES = ["pdeip_ac_solver", "pdeip_ac_solver_dev", "pdeip_reinit", "pdeip_reinit_dev", "pdeip_gac", "pdeip_gac_dev"]
+ENTRIES = ["pdeip_ac_solver", "pdeip_ac_solver_dev", "pdeip_reinit", "pdeip_reinit_dev", "pdeip_gac", "pdeip_gac_dev",
+           "pdeip_select_kth_dev", "pdeip_gac_stopping_dev"]
 
 
 def build_ls_stub(name, pdeip):
@@ -182,6 +183,32 @@ def test_gac_c_abi_refusals_need_no_gpu(pdeip):
     assert lib.pdeip_gac(p, 8, 8, 1, p, 7, None, p) == capi.PDEIP_ERR_ARG and "model" in capi.last_error()
     assert lib.pdeip_gac(p, 8, 8, 0, p, 0, None, p) == capi.PDEIP_ERR_ARG and "channels" in capi.last_error()
     assert lib.pdeip_gac_dev(None, p, 2, 8, 1, p, 0, None, p) == capi.PDEIP_ERR_ARG
+
+
+def test_gac_stage_entries_refuse_without_gpu(pdeip):
+    """pdeip_select_kth_dev and pdeip_gac_stopping_dev check their arguments before any HIP call."""
+    capi = pdeip.capi
+    lib = capi.load()
+    z = np.zeros((8, 8), np.float32, order="F")
+    o = np.zeros(4, np.float32)
+    p, q = z.ctypes.data, o.ctypes.data
+    for n, k, word in ((0, 1, "n must be"), (-3, 1, "n must be"), (2 ** 31, 1, "n must be"), (64, 0, "k must be"), (64, -1, "k must be"),
+                       (64, 65, "k must be")):
+        assert lib.pdeip_select_kth_dev(None, p, n, k, q) == capi.PDEIP_ERR_ARG and word in capi.last_error(), (n, k)
+    assert lib.pdeip_select_kth_dev(None, None, 64, 1, q) == capi.PDEIP_ERR_ARG and "NULL" in capi.last_error()
+    assert lib.pdeip_select_kth_dev(None, p, 64, 1, None) == capi.PDEIP_ERR_ARG and "NULL" in capi.last_error()
+    y = np.zeros((8, 8), np.float32, order="F")
+    w = np.zeros((8, 8), np.float32, order="F")
+    a, b = y.ctypes.data, w.ctypes.data
+    stop = lib.pdeip_gac_stopping_dev
+    assert stop(None, p, 2, 8, 1, -1.0, a, b, q) == capi.PDEIP_ERR_ARG and "at least 3x3" in capi.last_error()
+    assert stop(None, p, 8, 2, 1, -1.0, a, b, q) == capi.PDEIP_ERR_ARG and "at least 3x3" in capi.last_error()
+    assert stop(None, p, 8, 8, 0, -1.0, a, b, q) == capi.PDEIP_ERR_ARG and "channels" in capi.last_error()
+    assert stop(None, p, 46341, 46341, 1, -1.0, a, b, q) == capi.PDEIP_ERR_ARG and "too large" in capi.last_error()
+    for args in ((None, a, b, q), (p, None, b, q), (p, a, None, q), (p, a, b, None)):
+        assert stop(None, args[0], 8, 8, 1, -1.0, *args[1:]) == capi.PDEIP_ERR_ARG and "NULL" in capi.last_error()
+    for args in ((p, p, b), (p, a, p), (p, a, a)):
+        assert stop(None, args[0], 8, 8, 1, 0.5, args[1], args[2], q) == capi.PDEIP_ERR_ARG and "alias" in capi.last_error()
 
 
 def test_python_gac_drivers_reject_unknown_parameters(pdeip):
