@@ -757,6 +757,23 @@ int pdeip_surface_equation_dev(void *stream, const float *A, const float *B, int
 int pdeip_surface_fit_masked_dev(void *stream, const float *PHI, const float *D, int nrows, int ncols, int order, const float *M_in,
                                  float err_thr, float min_set_size, int iter, const unsigned *sets, unsigned long long seed,
                                  float *M_out, float *dist_out, int *ndata_out);
+/* The masked fit of S level-set planes PHI [nrows x ncols x S] over ONE data plane D [nrows x ncols] in one chain of launches:
+ * for every s in 0..S-1, column s of M_out [ncoef x S], plane s of dist_out (NULL ok) [nrows x ncols x S] and ndata_out[s] (device,
+ * NULL ok, [S]) equal, bit for bit, what
+ *   pdeip_surface_fit_masked_dev(stream, PHI + s*nrows*ncols, D, nrows, ncols, order, M_in ? M_in + s*ncoef : NULL, err_thr,
+ *                                min_set_size, iter, NULL, seed + seed_stride*s, ...)
+ * writes, the seed formed in 64-bit wrapping arithmetic; all that call defines holds per segment (a mask without pixels gives
+ * M_out = M_in, NaN when none was given; a singular winner gives FLT_MAX in dist; a NaN PHI is false).  M_in (NULL: no segment has
+ * a given model) is [ncoef x S].  There is no sets argument: the draws are seeded.  M_out may be M_in (models updated in place);
+ * dist_out must not alias PHI or D.  Asynchronous on `stream`: workspace from the library's cache (S*nrows*ncols ints, not the
+ * single call's data rows), one stream, no host read-back, no atomics, no graph branches (graph-capturable); at most 7 launches, 6
+ * without dist_out, whatever S is (pdeip_last_launch_count()).  Refused with PDEIP_ERR_ARG before any HIP call: a NULL PHI, D or
+ * M_out, S < 1 or S > 65535, order not 1 or 2, nrows or ncols < 1, a non-finite err_thr or min_set_size, iter <= 0 with M_in ==
+ * NULL, an iter the single call refuses, a workspace of more than 2^31-1 elements (S*nrows*ncols too large), dist_out == PHI or D.
+ * pdeip_set_mode does not apply. */
+int pdeip_surface_fit_masked_batch_dev(void *stream, const float *PHI, const float *D, int nrows, int ncols, int S, int order,
+                                       const float *M_in, float err_thr, float min_set_size, int iter, unsigned long long seed,
+                                       unsigned long long seed_stride, float *M_out, float *dist_out, int *ndata_out);
 
 /* ---- region competition: the inner loop of the segmentation drivers (csrc/pdeip_segmentation.hip) ---------------------------
  * What regionCompetition() does between its MEX calls (matlab/segmentation/DispSegmentation.m:497-646, DispSegmentationSparse.m:
@@ -767,10 +784,11 @@ int pdeip_surface_fit_masked_dev(void *stream, const float *PHI, const float *D,
  *               `recalc` set.  No segment left: the call returns at once with S_out = 0 and PDEIP_OK.
  *  2. terms     when iter is odd or recalc is set, (a)-(e), then recalc is cleared:
  *     (a) DH, gradPHI = pdeip_cv_terms(PHI, c0, c1, dh_floor).
- *     (b) per segment in order: pdeip_surface_fit_masked_dev with M_in = the segment's current model (a zero model IS a given
- *         model), err_thr, min_set_size = ransac_cset, 10 hypotheses, dist_out = the segment's dist plane.  The k-th fit a call
- *         performs (0-based, every fit counted, across iterations and scales) draws from seed + 65536*k in 64-bit wrapping
- *         arithmetic.  With nan_fill not NaN the fit and dist see D with every NaN replaced by nan_fill; D is not modified.
+ *     (b) all live segments in one pdeip_surface_fit_masked_batch_dev call, which is, per segment in order,
+ *         pdeip_surface_fit_masked_dev with M_in = the segment's current model (a zero model IS a given model), err_thr,
+ *         min_set_size = ransac_cset, 10 hypotheses, dist_out = the segment's dist plane.  The k-th fit a call performs (0-based,
+ *         every fit counted, across iterations and scales) draws from seed + 65536*k in 64-bit wrapping arithmetic: the batch
+ *         call's seed is that of its first segment, its seed_stride 65536.  With nan_fill not NaN the fit and dist see D with every NaN replaced by nan_fill; D is not modified.
  *     (c) n_s = the number of pixels with PHI_s >= 0 and, when dist_cap is finite, (double)dist < dist_cap (a NaN dist fails);
  *         cov_s = (sum of (double)dist over them) / n_s, the sum in float64 in a fixed order that depends neither on S nor on s
  *         (no floating-point atomics; with dist_cap = +Inf a NaN propagates); then if (cov_s < minCOV) cov_s = minCOV (a NaN

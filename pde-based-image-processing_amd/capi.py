@@ -140,6 +140,7 @@ SIGNATURES = {
     "pdeip_surface_equation": [_P, _P, _I, _I, _P, _F, _F, _I, _P, ctypes.c_ulonglong, _P, _P, _P, _P],
     "pdeip_surface_equation_dev": [_P, _P, _P, _I, _I, _P, _F, _F, _I, _P, ctypes.c_ulonglong, _P, _P, _P, _P],
     "pdeip_surface_fit_masked_dev": [_P, _P, _P, _I, _I, _I, _P, _F, _F, _I, _P, ctypes.c_ulonglong, _P, _P, _P],
+    "pdeip_surface_fit_masked_batch_dev": [_P, _P, _P, _I, _I, _I, _I, _P, _F, _F, _I, ctypes.c_ulonglong, ctypes.c_ulonglong, _P, _P, _P],
     # region competition (csrc/pdeip_segmentation.hip)
     "pdeip_seg_sizes_dev": [_P, _P, _I, _I, _I, _P],
     "pdeip_seg_variance_dev": [_P, _P, _P, _I, _I, _I, ctypes.c_double, ctypes.c_double, _P, _P],

@@ -4,14 +4,18 @@
 //                                                                              pdeip_surface_equation(_dev)
 //   the fit on the pixels with PHI >= 0 of the segmentation drivers, resident (DispSegmentation.m:329-360)
 //                                                                              pdeip_surface_fit_masked_dev
+//   the same fit of S level-set planes over one data plane in one chain (region competition's fit stage)
+//                                                                              pdeip_surface_fit_masked_batch_dev
 //
-// Kernels: csrc/pdeip_ransac.hpp; the contract: include/pdeip.h.  pdeip_set_mode does not apply.
+// Kernels: csrc/pdeip_ransac.hpp, csrc/pdeip_ransac_batch.hpp; the contract: include/pdeip.h.  pdeip_set_mode does not apply.
 //
 // Build (build.py): hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -c, one object per translation unit.
 #include "pdeip_ctx.hpp"
 #include "pdeip_ransac.hpp"
+#include "pdeip_ransac_batch.hpp"
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 
 using namespace pdeip;
@@ -184,4 +188,95 @@ extern "C" int pdeip_surface_fit_masked_dev(void *stream, const float *PHI, cons
         tls.last_launches++;
     }
     return PDEIP_OK;
+}
+
+// ---- S masks over one data plane in one chain ---------------------------------------------------------------------------------------
+namespace {
+
+// The batch call's workspace (WS_RANSAC_BATCH, its own slot: a single fit between two batch calls leaves it alone), the doubles
+// first.  Returns its size in floats; every part starts at a multiple of 4 floats.
+size_t batch_carve(float *ws, int S, int npix, int H, BatchWs *b)
+{
+    const int nblk = (npix + RS_BLOCK - 1) / RS_BLOCK;
+    const size_t tiles = chain_tiles(npix), np = (size_t)S * tiles * H, lda = up4((size_t)npix), ldb = up4((size_t)nblk);
+    const size_t oCnt = 2 * up4(np), oModels = oCnt + up4(np), oWin = oModels + (size_t)S * H * RS_SLOT, oIdx = oWin + (size_t)S * RS_SLOT;
+    const size_t oBlk = oIdx + (size_t)S * lda, oN = oBlk + (size_t)S * ldb, total = oN + up4((size_t)S);
+    if (b != nullptr) {
+        b->psum = reinterpret_cast<double *>(ws);
+        b->pcnt = reinterpret_cast<int *>(ws + oCnt);
+        b->models = ws + oModels;
+        b->win = ws + oWin;
+        b->idx = reinterpret_cast<int *>(ws + oIdx);
+        b->blk = reinterpret_cast<int *>(ws + oBlk);
+        b->ndata = reinterpret_cast<int *>(ws + oN);
+        b->lda = (int)lda;
+        b->ldb = (int)ldb;
+        b->tiles = (int)tiles;
+    }
+    return total;
+}
+
+template <int NC>
+int run_batch(hipStream_t s, const BatchWs &w, const float *PHI, const float *D, int nrows, int ncols, int S, const float *M_in, float err_thr,
+              float min_set_size, int it, unsigned long long seed, unsigned long long seed_stride, float *M_out, float *dist_out, int *ndata_out)
+{
+    const int npix = nrows * ncols, H = it + 1, nblk = (npix + RS_BLOCK - 1) / RS_BLOCK;
+    const int R = rows_per_thread(npix);
+    // hypotheses per score block from all the blocks of the call: with few slots and many segments one block takes a tile's every slot
+    int G = (int)std::min<long long>(RS_GMAX, std::max<long long>(1, (long long)H * w.tiles * S / RS_WANT_BLOCKS));
+    G = std::max(G, (H + 65534) / 65535);
+    const float thr2 = err_thr * err_thr;
+    const dim3 pix((unsigned)nblk, (unsigned)S);
+    hipLaunchKernelGGL(k_maskb_count, pix, dim3(RS_BLOCK), 0, s, PHI, npix, w.blk, w.ldb);
+    hipLaunchKernelGGL(k_maskb_scan, dim3((unsigned)S), dim3(RS_SEL_BLOCK), 0, s, w.blk, w.ldb, nblk, w.ndata, ndata_out);
+    hipLaunchKernelGGL(k_maskb_scatter, pix, dim3(RS_BLOCK), 0, s, PHI, npix, w.blk, w.ldb, w.idx, w.lda);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_fitb<NC>, dim3((unsigned)(((long long)S * H + 63) / 64)), dim3(64), 0, s, w.idx, w.lda, D, nrows, w.ndata, S, seed,
+                       seed_stride, H, M_in, w.models);
+    HIPCHK(hipGetLastError());
+    const dim3 grid((unsigned)w.tiles, (unsigned)((H + G - 1) / G), (unsigned)S);
+    if (R == 1)
+        hipLaunchKernelGGL((k_scoreb<NC, 1>), grid, dim3(RS_BLOCK), 0, s, w.idx, w.lda, D, nrows, w.ndata, w.models, H, G, thr2, w.psum, w.pcnt);
+    else
+        hipLaunchKernelGGL((k_scoreb<NC, RS_R_BIG>), grid, dim3(RS_BLOCK), 0, s, w.idx, w.lda, D, nrows, w.ndata, w.models, H, G, thr2, w.psum, w.pcnt);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_selectb, dim3((unsigned)S), dim3(RS_SEL_BLOCK), 0, s, w.psum, w.pcnt, H, w.tiles, w.ndata, RS_BLOCK * R, w.models,
+                       M_in != nullptr ? 1 : 0, min_set_size, NC, M_out, w.win);
+    HIPCHK(hipGetLastError());
+    tls.last_launches = 6;
+    if (dist_out != nullptr) {
+        hipLaunchKernelGGL(k_distb<NC>, pix, dim3(RS_BLOCK), 0, s, D, nrows, npix, w.win, dist_out);
+        HIPCHK(hipGetLastError());
+        tls.last_launches++;
+    }
+    return PDEIP_OK;
+}
+
+} // namespace
+
+extern "C" int pdeip_surface_fit_masked_batch_dev(void *stream, const float *PHI, const float *D, int nrows, int ncols, int S, int order,
+                                                  const float *M_in, float err_thr, float min_set_size, int iter, unsigned long long seed,
+                                                  unsigned long long seed_stride, float *M_out, float *dist_out, int *ndata_out)
+{
+    const char *who = "pdeip_surface_fit_masked_batch_dev";
+    NONNULL(who, PHI); NONNULL(who, D); NONNULL(who, M_out);
+    if (S < 1 || S > 65535) return set_err(PDEIP_ERR_ARG, "%s: S must lie in 1 .. 65535 (got %d)", who, S);
+    if (order != 1 && order != 2) return set_err(PDEIP_ERR_ARG, "%s: order must be 1 or 2 (got %d)", who, order);
+    const int ncoef = order == 1 ? 3 : 6;
+    RC(check_common(who, ncoef, err_thr, min_set_size, iter, M_in));
+    if (nrows < 1 || ncols < 1) return set_err(PDEIP_ERR_ARG, "%s: PHI must not be empty (got %dx%d)", who, nrows, ncols);
+    if ((long long)nrows * ncols > 0x7fffffffLL / 8) return set_err(PDEIP_ERR_ARG, "%s: image too large", who);
+    const int npix = nrows * ncols, it = iter > 0 ? iter : 0;
+    const size_t floats = batch_carve(nullptr, S, npix, it + 1, nullptr);
+    if (floats > (size_t)INT_MAX)
+        return set_err(PDEIP_ERR_ARG, "%s: the workspace of %d planes of %dx%d with %d hypotheses has more than 2^31-1 elements", who, S, nrows, ncols, it);
+    if (dist_out != nullptr && (dist_out == PHI || dist_out == D)) return set_err(PDEIP_ERR_ARG, "%s: dist_out must not alias PHI or D", who);
+    tls.last_launches = 0;
+    float *ws = nullptr;
+    RC(ws_get(WS_RANSAC_BATCH, floats * sizeof(float), &ws));
+    BatchWs w;
+    batch_carve(ws, S, npix, it + 1, &w);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (ncoef == 3) return run_batch<3>(s, w, PHI, D, nrows, ncols, S, M_in, err_thr, min_set_size, it, seed, seed_stride, M_out, dist_out, ndata_out);
+    return run_batch<6>(s, w, PHI, D, nrows, ncols, S, M_in, err_thr, min_set_size, it, seed, seed_stride, M_out, dist_out, ndata_out);
 }

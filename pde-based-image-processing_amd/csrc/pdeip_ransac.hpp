@@ -65,38 +65,11 @@ __device__ __forceinline__ void pixel_row(int i, int j, float (&a)[NC])
 //                     R[k][k] = alpha
 //   for k = NC-1..0:  t = b[k];  for j = k+1..NC-1: t = t - R[k][j]*x[j];  x[k] = t / R[k][k]
 // An index >= ndata (the device forms cannot refuse it) makes the hypothesis singular; nothing is read through it.
+// fit_solve: the solve on the gathered samples R (column NC: the right-hand side), and the model slot it fills.
 template <int NC>
-__global__ void __launch_bounds__(64) k_ransac_fit(const float *__restrict__ A, const float *__restrict__ B, int lda, int ndata_h,
-                                                   const int *__restrict__ ndata_d, const unsigned *__restrict__ sets,
-                                                   unsigned long long seed, int iter, const float *__restrict__ M_in,
-                                                   float *__restrict__ models)
+__device__ __forceinline__ void fit_solve(double (&R)[NC + 1][NC + 1], bool singular, float *__restrict__ out)
 {
     constexpr int N = NC + 1;
-    const int slot = blockIdx.x * 64 + threadIdx.x;
-    if (slot > iter) return;
-    float *out = models + (size_t)slot * RS_SLOT;
-    if (slot == 0) {
-#pragma unroll
-        for (int c = 0; c < 6; c++) out[c] = (M_in != nullptr && c < NC) ? M_in[c] : 0.0f;
-        out[6] = M_in != nullptr ? 0.0f : 1.0f;
-        out[7] = 0.0f;
-        return;
-    }
-    const unsigned ndata = (unsigned)rows_of(ndata_h, ndata_d);
-    const unsigned long long h = (unsigned long long)(slot - 1);
-    double R[N][NC + 1]; // column NC: the right-hand side
-    bool singular = false;
-#pragma unroll
-    for (int k = 0; k < N; k++) {
-        unsigned idx;
-        if (sets != nullptr) idx = sets[h * N + k];
-        else idx = (unsigned)(((splitmix64(seed + h * N + k) >> 32) * (unsigned long long)ndata) >> 32);
-        const bool ok = idx < ndata;
-        singular = singular || !ok;
-#pragma unroll
-        for (int c = 0; c < NC; c++) R[k][c] = ok ? (double)A[(size_t)c * lda + idx] : 0.0;
-        R[k][NC] = ok ? (double)B[idx] : 0.0;
-    }
 #pragma unroll
     for (int k = 0; k < NC; k++) {
         double s = 0.0;
@@ -137,6 +110,41 @@ __global__ void __launch_bounds__(64) k_ransac_fit(const float *__restrict__ A, 
     out[7] = 0.0f;
 }
 
+template <int NC>
+__global__ void __launch_bounds__(64) k_ransac_fit(const float *__restrict__ A, const float *__restrict__ B, int lda, int ndata_h,
+                                                   const int *__restrict__ ndata_d, const unsigned *__restrict__ sets,
+                                                   unsigned long long seed, int iter, const float *__restrict__ M_in,
+                                                   float *__restrict__ models)
+{
+    constexpr int N = NC + 1;
+    const int slot = blockIdx.x * 64 + threadIdx.x;
+    if (slot > iter) return;
+    float *out = models + (size_t)slot * RS_SLOT;
+    if (slot == 0) {
+#pragma unroll
+        for (int c = 0; c < 6; c++) out[c] = (M_in != nullptr && c < NC) ? M_in[c] : 0.0f;
+        out[6] = M_in != nullptr ? 0.0f : 1.0f;
+        out[7] = 0.0f;
+        return;
+    }
+    const unsigned ndata = (unsigned)rows_of(ndata_h, ndata_d);
+    const unsigned long long h = (unsigned long long)(slot - 1);
+    double R[N][NC + 1]; // column NC: the right-hand side
+    bool singular = false;
+#pragma unroll
+    for (int k = 0; k < N; k++) {
+        unsigned idx;
+        if (sets != nullptr) idx = sets[h * N + k];
+        else idx = (unsigned)(((splitmix64(seed + h * N + k) >> 32) * (unsigned long long)ndata) >> 32);
+        const bool ok = idx < ndata;
+        singular = singular || !ok;
+#pragma unroll
+        for (int c = 0; c < NC; c++) R[k][c] = ok ? (double)A[(size_t)c * lda + idx] : 0.0;
+        R[k][NC] = ok ? (double)B[idx] : 0.0;
+    }
+    fit_solve<NC>(R, singular, out);
+}
+
 // ---- score: grid (data tiles, hypothesis groups); a tile is RS_BLOCK * R rows, thread t holds rows row0 + r*RS_BLOCK + t ----------
 // Per hypothesis: the thread's float64 sum over its inlier rows in ascending r, the xor butterfly over the wave (partners 32, 16,
 // .. 1 lanes apart), the four waves in ascending order; the count by ballot + popcount.  One (count, sum) per (tile, hypothesis) is
@@ -150,29 +158,14 @@ __device__ __forceinline__ double pair_step(double even, double odd, bool upper,
     return (upper ? odd : even) + __shfl_xor(upper ? even : odd, d, 64);
 }
 
+// The block's part of the scores of `ng` hypotheses on the rows it holds: models, psum and pcnt start at the block's first hypothesis.
 template <int NC, int R>
-__global__ void __launch_bounds__(RS_BLOCK) k_ransac_score(const float *__restrict__ A, const float *__restrict__ B, int lda, int ndata_h,
-                                                           const int *__restrict__ ndata_d, const float *__restrict__ models, int H,
-                                                           int G, float thr2, double *__restrict__ psum, int *__restrict__ pcnt)
+__device__ __forceinline__ void score_rows(const float (&a)[R][NC], const float (&b)[R], const bool (&ok)[R], const float *__restrict__ models,
+                                           int ng, float thr2, double *__restrict__ psum, int *__restrict__ pcnt)
 {
     __shared__ double s_sum[RS_WAVES][RS_GMAX];
     __shared__ int s_cnt[RS_WAVES][RS_GMAX];
-    const int ndata = rows_of(ndata_h, ndata_d);
-    const long long row0 = (long long)blockIdx.x * (RS_BLOCK * R);
-    if (row0 >= ndata) return; // the masked form sizes the grid for every pixel
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int h0 = blockIdx.y * G;
-    const int ng = min(G, H - h0);
-    float a[R][NC], b[R];
-    bool ok[R];
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        const long long row = row0 + (long long)r * RS_BLOCK + tid;
-        ok[r] = row < ndata;
-#pragma unroll
-        for (int c = 0; c < NC; c++) a[r][c] = ok[r] ? A[(size_t)c * lda + row] : 0.0f;
-        b[r] = ok[r] ? B[row] : 0.0f;
-    }
     const bool b5 = (lane & 32) != 0, b4 = (lane & 16) != 0, b3 = (lane & 8) != 0;
     const int mine = (b3 ? 4 : 0) + (b4 ? 2 : 0) + (b5 ? 1 : 0); // the hypothesis of a batch whose sum this lane ends up with
     for (int g0 = 0; g0 < ng; g0 += RS_BATCH) {
@@ -182,7 +175,7 @@ __global__ void __launch_bounds__(RS_BLOCK) k_ransac_score(const float *__restri
         for (int j = 0; j < RS_BATCH; j++) {
             s[j] = 0.0;
             if (g0 + j < ng) {
-                const float *ms = models + (size_t)(h0 + g0 + j) * RS_SLOT; // wave-uniform: scalar loads
+                const float *ms = models + (size_t)(g0 + j) * RS_SLOT; // wave-uniform: scalar loads
                 float m[NC];
 #pragma unroll
                 for (int c = 0; c < NC; c++) m[c] = ms[c];
@@ -219,24 +212,45 @@ __global__ void __launch_bounds__(RS_BLOCK) k_ransac_score(const float *__restri
             s = s + s_sum[w][tid];
             cnt += s_cnt[w][tid];
         }
-        const size_t at = (size_t)blockIdx.x * H + (h0 + tid);
-        psum[at] = s;
-        pcnt[at] = cnt;
+        psum[tid] = s;
+        pcnt[tid] = cnt;
     }
+}
+
+template <int NC, int R>
+__global__ void __launch_bounds__(RS_BLOCK) k_ransac_score(const float *__restrict__ A, const float *__restrict__ B, int lda, int ndata_h,
+                                                           const int *__restrict__ ndata_d, const float *__restrict__ models, int H,
+                                                           int G, float thr2, double *__restrict__ psum, int *__restrict__ pcnt)
+{
+    const int ndata = rows_of(ndata_h, ndata_d);
+    const long long row0 = (long long)blockIdx.x * (RS_BLOCK * R);
+    if (row0 >= ndata) return; // the masked form sizes the grid for every pixel
+    const int tid = threadIdx.x;
+    const int h0 = blockIdx.y * G;
+    const int ng = min(G, H - h0);
+    float a[R][NC], b[R];
+    bool ok[R];
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        const long long row = row0 + (long long)r * RS_BLOCK + tid;
+        ok[r] = row < ndata;
+#pragma unroll
+        for (int c = 0; c < NC; c++) a[r][c] = ok[r] ? A[(size_t)c * lda + row] : 0.0f;
+        b[r] = ok[r] ? B[row] : 0.0f;
+    }
+    score_rows<NC, R>(a, b, ok, models + (size_t)h0 * RS_SLOT, ng, thr2, psum + ((size_t)blockIdx.x * H + h0), pcnt + ((size_t)blockIdx.x * H + h0));
 }
 
 // ---- select: one workgroup ------------------------------------------------------------------------------------------------------
 // Totals: per hypothesis the tile partials in ascending tile order.  Then thread 0 walks the slots in order with RANSAC()'s rules
 // (ransac.c:112-211) and writes the winner's slot to `win` and its coefficients to M_out.
-__global__ void __launch_bounds__(RS_SEL_BLOCK) k_ransac_select(const double *__restrict__ psum, const int *__restrict__ pcnt, int H,
-                                                                int ndata_h, const int *__restrict__ ndata_d, int tile_rows,
-                                                                const float *__restrict__ models, int has_given, float min_set_size,
-                                                                int ncoef, float *__restrict__ M_out, float *__restrict__ win,
-                                                                int *__restrict__ inliers_out, double *__restrict__ errsum_out)
+__device__ __forceinline__ void select_winner(const double *__restrict__ psum, const int *__restrict__ pcnt, int H, int ndata, int tile_rows,
+                                              const float *__restrict__ models, int has_given, float min_set_size, int ncoef,
+                                              float *__restrict__ M_out, float *__restrict__ win, int *__restrict__ inliers_out,
+                                              double *__restrict__ errsum_out)
 {
     __shared__ double s_sum[RS_SEL_CHUNK];
     __shared__ int s_cnt[RS_SEL_CHUNK];
-    const int ndata = rows_of(ndata_h, ndata_d);
     const int tiles = ndata / tile_rows + (ndata % tile_rows != 0 ? 1 : 0);
     const int tid = threadIdx.x;
     // abs_min = (unsigned)(min_set_size*(float)ndata + 0.5f); below 1 (negative included) it is 0, from 2^32 on it is 2^32 - 1
@@ -296,6 +310,15 @@ __global__ void __launch_bounds__(RS_SEL_BLOCK) k_ransac_select(const double *__
     }
 }
 
+__global__ void __launch_bounds__(RS_SEL_BLOCK) k_ransac_select(const double *__restrict__ psum, const int *__restrict__ pcnt, int H,
+                                                                int ndata_h, const int *__restrict__ ndata_d, int tile_rows,
+                                                                const float *__restrict__ models, int has_given, float min_set_size,
+                                                                int ncoef, float *__restrict__ M_out, float *__restrict__ win,
+                                                                int *__restrict__ inliers_out, double *__restrict__ errsum_out)
+{
+    select_winner(psum, pcnt, H, rows_of(ndata_h, ndata_d), tile_rows, models, has_given, min_set_size, ncoef, M_out, win, inliers_out, errsum_out);
+}
+
 // ---- the winner's errors --------------------------------------------------------------------------------------------------------
 template <int NC>
 __global__ void __launch_bounds__(RS_BLOCK) k_ransac_errors(const float *__restrict__ A, const float *__restrict__ B, int lda, int ndata_h,
@@ -316,7 +339,7 @@ __global__ void __launch_bounds__(RS_BLOCK) k_ransac_errors(const float *__restr
 
 // ---- the masked form ------------------------------------------------------------------------------------------------------------
 // Pixels in memory (column-major) order; PHI >= 0 is false for a NaN.  One block ranks RS_BLOCK pixels.
-__global__ void __launch_bounds__(RS_BLOCK) k_mask_count(const float *__restrict__ PHI, int npix, int *__restrict__ blk_cnt)
+__device__ __forceinline__ void mask_count(const float *__restrict__ PHI, int npix, int *__restrict__ blk_cnt)
 {
     __shared__ int s_w[RS_WAVES];
     const int p = blockIdx.x * RS_BLOCK + threadIdx.x;
@@ -327,8 +350,13 @@ __global__ void __launch_bounds__(RS_BLOCK) k_mask_count(const float *__restrict
     if (threadIdx.x == 0) blk_cnt[blockIdx.x] = (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
 }
 
+__global__ void __launch_bounds__(RS_BLOCK) k_mask_count(const float *__restrict__ PHI, int npix, int *__restrict__ blk_cnt)
+{
+    mask_count(PHI, npix, blk_cnt);
+}
+
 // Exclusive prefix sum of the block counts, in place, by one workgroup; the total goes to ndata[0] and ndata_out[0].
-__global__ void __launch_bounds__(RS_SEL_BLOCK) k_mask_scan(int *__restrict__ blk, int nblk, int *__restrict__ ndata, int *__restrict__ ndata_out)
+__device__ __forceinline__ void mask_scan(int *__restrict__ blk, int nblk, int *__restrict__ ndata, int *__restrict__ ndata_out)
 {
     __shared__ int s[RS_SEL_BLOCK];
     __shared__ int s_carry;
@@ -358,10 +386,14 @@ __global__ void __launch_bounds__(RS_SEL_BLOCK) k_mask_scan(int *__restrict__ bl
     }
 }
 
+__global__ void __launch_bounds__(RS_SEL_BLOCK) k_mask_scan(int *__restrict__ blk, int nblk, int *__restrict__ ndata, int *__restrict__ ndata_out)
+{
+    mask_scan(blk, nblk, ndata, ndata_out);
+}
+
 // Writes row rank(p) of the compacted A (columns lda apart) and B for every pixel p with PHI >= 0.
-template <int NC>
-__global__ void __launch_bounds__(RS_BLOCK) k_mask_scatter(const float *__restrict__ PHI, const float *__restrict__ D, int nrows, int npix,
-                                                           const int *__restrict__ blk_off, float *__restrict__ A, int lda, float *__restrict__ B)
+// The rank of pixel p = blockIdx.x * RS_BLOCK + threadIdx.x among the pixels with PHI >= 0, or -1 when it is not one of them.
+__device__ __forceinline__ int mask_rank(const float *__restrict__ PHI, int npix, const int *__restrict__ blk_off)
 {
     __shared__ int s_w[RS_WAVES];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -370,9 +402,19 @@ __global__ void __launch_bounds__(RS_BLOCK) k_mask_scatter(const float *__restri
     const unsigned long long bal = __ballot(in);
     if (lane == 0) s_w[wave] = __popcll(bal);
     __syncthreads();
-    if (!in) return;
+    if (!in) return -1;
     int rank = blk_off[blockIdx.x] + __popcll(bal & ((1ull << lane) - 1ull));
     for (int w = 0; w < wave; w++) rank += s_w[w];
+    return rank;
+}
+
+template <int NC>
+__global__ void __launch_bounds__(RS_BLOCK) k_mask_scatter(const float *__restrict__ PHI, const float *__restrict__ D, int nrows, int npix,
+                                                           const int *__restrict__ blk_off, float *__restrict__ A, int lda, float *__restrict__ B)
+{
+    const int p = blockIdx.x * RS_BLOCK + threadIdx.x;
+    const int rank = mask_rank(PHI, npix, blk_off);
+    if (rank < 0) return;
     float a[NC];
     pixel_row<NC>(p % nrows, p / nrows, a);
 #pragma unroll

@@ -13,8 +13,9 @@
 // and generateSeeds()'s starting gamma are passed in (Form below).
 //
 // Kernels: csrc/pdeip_segmentation.hpp; the seed loop's host-side schedule: csrc/pdeip_seeds_plan.hpp, the sparse forms' plan:
-// csrc/pdeip_sparse_plan.hpp (the pyramid itself: csrc/pdeip_sparse.hip); the contract: include/pdeip.h.  The fit is pdeip_surface_fit_masked_dev, the terms and the
-// step pdeip_cv_terms_dev / pdeip_cv_solver_dev.  pdeip_set_mode does not apply.
+// csrc/pdeip_sparse_plan.hpp (the pyramid itself: csrc/pdeip_sparse.hip); the contract: include/pdeip.h.  The fit is
+// pdeip_surface_fit_masked_batch_dev (a level: all live segments in one chain) or pdeip_surface_fit_masked_dev (generateSeeds: one
+// segment at a time), the terms and the step pdeip_cv_terms_dev / pdeip_cv_solver_dev.  pdeip_set_mode does not apply.
 //
 // Build (build.py): hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -c, one object per translation unit.
 #include "pdeip_ctx.hpp"
@@ -285,6 +286,7 @@ extern "C" int pdeip_seg_competition_level_dev(void *stream, const float *PHI, c
     int *host_sizes = nullptr;
     RC(pinned_sizes(S, &host_sizes));
 
+    const bool fit_chains = env_int("PDEIP_SEG_FIT_CHAINS", 0) != 0; // 1: one single-fit chain per segment (the A/B switch of tools/time_segmentation.py)
     int launches = 0;
     RC(copy_d2d(s, cur, PHI, (size_t)S * npix));
     const float *Dsrc = D;
@@ -327,12 +329,19 @@ extern "C" int pdeip_seg_competition_level_dev(void *stream, const float *PHI, c
         if ((it & 1) || recalc) {
             RC(pdeip_cv_terms_dev(s, cur, nrows, ncols, live, p.c0, p.c1, p.dh_floor, DH, GRAD));
             launches += 1;
-            for (int k = 0; k < live; k++) {
-                float *M = models + (size_t)k * ncoef;
-                RC(pdeip_surface_fit_masked_dev(s, cur + (size_t)k * npix, Dsrc, nrows, ncols, order, M, p.err_thr, ransac_cset, 10, nullptr,
-                                                seed + 65536ull * fit, M, DIST + (size_t)k * npix, nullptr));
+            if (!fit_chains && live <= 65535) { // every live segment's fit in one chain: segment k draws from seed + 65536*(fit + k)
+                RC(pdeip_surface_fit_masked_batch_dev(s, cur, Dsrc, nrows, ncols, live, order, models, p.err_thr, ransac_cset, 10,
+                                                      seed + 65536ull * fit, 65536ull, models, DIST, nullptr));
                 launches += tls.last_launches;
-                fit++;
+                fit += (unsigned long long)live;
+            } else {
+                for (int k = 0; k < live; k++) {
+                    float *M = models + (size_t)k * ncoef;
+                    RC(pdeip_surface_fit_masked_dev(s, cur + (size_t)k * npix, Dsrc, nrows, ncols, order, M, p.err_thr, ransac_cset, 10, nullptr,
+                                                    seed + 65536ull * fit, M, DIST + (size_t)k * npix, nullptr));
+                    launches += tls.last_launches;
+                    fit++;
+                }
             }
             RC(launch_variance(s, cur, DIST, npix, live, minCOV, p.dist_cap, psum, pcnt, cov, nullptr));
             RC(launch_data(s, DIST, cur, DH, cov, npix, live, strategy, DATA, nullptr));

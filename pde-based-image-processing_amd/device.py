@@ -257,6 +257,27 @@ def surface_fit_masked(PHI, D, order, M_in, err_thr, min_set_size, iter, M_out, 
               opt(ndata_out))
 
 
+def surface_fit_masked_batch(PHI, D, order, M_in, err_thr, min_set_size, iter, M_out, dist_out=None, ndata_out=None, seed=0, seed_stride=65536):
+    """surface_fit_masked of S planes PHI [S, ncols, nrows] over one data plane D [ncols, nrows] in one chain of launches
+    (pdeip_surface_fit_masked_batch_dev): segment s draws from seed + seed_stride*s.  M_in float32 [S, 3 | 6] or None; M_out
+    float32 [S, 3 | 6] (may be M_in); dist_out [S, ncols, nrows] or None; ndata_out an int32 tensor of S elements or None.
+    Nothing is read back."""
+    _chk(PHI, D, M_out, *[t for t in (M_in, dist_out) if t is not None])
+    if PHI.dim() != 3 or D.dim() != 2 or D.shape != PHI.shape[1:] or (dist_out is not None and dist_out.shape != PHI.shape):
+        raise capi.PdeipError(capi.PDEIP_ERR_ARG, "surface_fit_masked_batch: PHI and dist_out must be [S, ncols, nrows], D one plane of that size")
+    nrows, ncols, S = _dims(PHI)
+    ncoef = 3 if order == 1 else 6
+    if M_out.numel() != S * ncoef or (M_in is not None and M_in.numel() != S * ncoef):
+        raise capi.PdeipError(capi.PDEIP_ERR_ARG, "surface_fit_masked_batch: M_in and M_out must have S x %d elements" % ncoef)
+    if ndata_out is not None and (ndata_out.dtype != torch.int32 or not ndata_out.is_cuda or not ndata_out.is_contiguous() or ndata_out.numel() != S):
+        raise capi.PdeipError(capi.PDEIP_ERR_ARG, "surface_fit_masked_batch: ndata_out must be a contiguous int32 CUDA tensor of S elements")
+    opt = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    m64 = (1 << 64) - 1
+    capi.call("pdeip_surface_fit_masked_batch_dev", _stream(), PHI.data_ptr(), D.data_ptr(), nrows, ncols, S, int(order), opt(M_in),
+              float(err_thr), float(min_set_size), int(iter), ctypes.c_ulonglong(int(seed) & m64), ctypes.c_ulonglong(int(seed_stride) & m64),
+              M_out.data_ptr(), opt(dist_out), opt(ndata_out))
+
+
 class Diffusion4Params(ctypes.Structure):
     """pdeip_diffusion4_params: NaN keeps the driver's default (alpha 25, outer_iter 5)."""
     _fields_ = [("alpha", ctypes.c_double), ("outer_iter", ctypes.c_double)]

@@ -5,12 +5,17 @@
 The parent process never touches the GPU.  It runs two child steps, each under its own time limit, and stops at the first
 that fails (nothing is retried):
   1. timing: ms per pdeip_seg_competition_level_dev call of 30 iterations at 115x154x15 and 288x384x15 (the drivers' rc_scl
-     scale and full scale), dense `inverse`, orders 1 and 2, no segment removed; beside it the wall time of the 15 per-segment
-     fit chains of one odd iteration (fits_us) and of an even iteration's sizes + read-back + Chan-Vese step (even_us), from
-     which odd_us = (level - 15*even_us)/15 and fit_share = fits_us/odd_us; and the NumPy restatement
-     (tests/segmentation_ref.py) of the same level on the host, timed on 2 iterations and scaled to 30 (ref_ms, an
-     extrapolation; the restatement is a checker, not a baseline);
-  2. `rocprofv3 --kernel-trace --stats` of one 288x384x15 order-1 level: calls and total us per kernel.
+     scale and full scale), dense `inverse`, orders 1 and 2, no segment removed, and the wall time of the fit stage of one odd
+     iteration, each in both forms -- `batched` (one pdeip_surface_fit_masked_batch_dev call, the default) and `chained` (one
+     pdeip_surface_fit_masked_dev chain per segment, PDEIP_SEG_FIT_CHAINS=1: the form before the batch call existed and the
+     baseline) -- alternated --ab times in this one process on this one device; a sample is the mean of --reps calls enqueued
+     back to back and synchronised once, as the level enqueues them.  Reported per form: median, min and max of the samples.
+     `batched_wins` holds where the chained median exceeds the batched one by more than the spread (the larger max - min of
+     the two forms).  Beside it an even iteration's sizes + read-back + Chan-Vese step (even_us), from which per form odd_us =
+     (level - 15*even_us)/15 and fit_share = fit_us/odd_us; and the NumPy restatement (tests/segmentation_ref.py) of the same
+     level on the host, timed on 2 iterations and scaled to 30 (ref_ms, an extrapolation; the restatement is a checker, not a
+     baseline);
+  2. `rocprofv3 --kernel-trace --stats` of one 288x384x15 order-1 level (the default form): calls and total us per kernel.
 """
 import argparse
 import csv
@@ -26,8 +31,11 @@ ROOT = os.path.abspath(os.path.join(os.path.dirname(os.path.abspath(__file__)), 
 SHAPES = [(115, 154), (288, 384)]
 SEGMENTS, ITERATIONS, REF_ITERATIONS = 15, 30, 2
 KERNELS = ("k_seg_sizes_final", "k_seg_sizes", "k_seg_variance_final", "k_seg_variance", "k_seg_data", "k_cv_terms", "k_cv_lines", "k_cv_combine",
-           "k_mask_count", "k_mask_scan", "k_mask_scatter", "k_ransac_fit", "k_ransac_score", "k_ransac_select", "k_ransac_dist", "k_copy_d2d")
-FIT_KERNELS = ("k_mask_count", "k_mask_scan", "k_mask_scatter", "k_ransac_fit", "k_ransac_score", "k_ransac_select", "k_ransac_dist")
+           "k_mask_count", "k_mask_scan", "k_mask_scatter", "k_ransac_fit", "k_ransac_score", "k_ransac_select", "k_ransac_dist",
+           "k_maskb_count", "k_maskb_scan", "k_maskb_scatter", "k_fitb", "k_scoreb", "k_selectb", "k_distb", "k_copy_d2d")
+FIT_KERNELS = KERNELS[KERNELS.index("k_mask_count"):KERNELS.index("k_copy_d2d")]
+FORMS = ("batched", "chained")
+SWITCH = "PDEIP_SEG_FIT_CHAINS"
 
 
 def _inputs(nr, nc):
@@ -48,7 +56,13 @@ def _inputs(nr, nc):
     return np.asfortranarray(D.astype(np.float32)), np.asfortranarray(PHI)
 
 
-def _child_timing(reps, kernels_only):
+def _stats(samples):
+    import statistics
+
+    return {"median": statistics.median(samples), "min": min(samples), "max": max(samples), "n": len(samples)}
+
+
+def _child_timing(reps, kernels_only, ab=5):
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import importlib
@@ -85,14 +99,34 @@ def _child_timing(reps, kernels_only):
             level()
             torch.cuda.synchronize()
             continue
-        r = {"level_ms": wall(level, reps) * 1e3, "S_out": S_out[-1]}
         M = torch.zeros((SEGMENTS, 3 if order == 1 else 6), dtype=torch.float32, device="cuda")
         dist, DATA, DH, G, nxt = (torch.empty_like(P) for _ in range(5))
         sizes = torch.zeros(SEGMENTS, dtype=torch.int32, device="cuda")
 
-        def fits():
+        def fits_chained():
             for k in range(SEGMENTS):
                 dev.surface_fit_masked(P[k], Dd, order, M[k], 1.0, 0.7, 10, M[k], dist[k], None, seed=k)
+
+        def fits_batched():
+            dev.surface_fit_masked_batch(P, Dd, order, M, 1.0, 0.7, 10, M, dist, None, seed=0, seed_stride=1)
+
+        fits = {"batched": fits_batched, "chained": fits_chained}
+        fit_us, level_ms = {f: [] for f in FORMS}, {f: [] for f in FORMS}
+        for _ in range(ab):  # the two forms in turn, so that a drift of the device or the host falls on both
+            for form in FORMS:
+                M.zero_()
+                fit_us[form].append(wall(fits[form], reps) * 1e6)
+                os.environ.pop(SWITCH, None)
+                if form == "chained":
+                    os.environ[SWITCH] = "1"
+                try:
+                    level_ms[form].append(wall(level, reps) * 1e3)
+                finally:
+                    os.environ.pop(SWITCH, None)
+        r = {"S_out": S_out[-1], "fit_us": {f: _stats(fit_us[f]) for f in FORMS}, "level_ms": {f: _stats(level_ms[f]) for f in FORMS}}
+        spread = max(r["fit_us"][f]["max"] - r["fit_us"][f]["min"] for f in FORMS)
+        r["fit_us"]["spread"] = spread
+        r["batched_wins"] = r["fit_us"]["chained"]["median"] - r["fit_us"]["batched"]["median"] > spread
 
         def even():
             dev.seg_sizes(P, sizes)
@@ -101,10 +135,9 @@ def _child_timing(reps, kernels_only):
 
         dev.cv_terms(P, 1.0, 1.0, 0.06, DH, G)
         DATA.zero_()
-        r["fits_us"] = wall(fits, reps) * 1e6
         r["even_us"] = wall(even, reps) * 1e6
-        r["odd_us"] = (r["level_ms"] * 1e3 - (ITERATIONS // 2) * r["even_us"]) / (ITERATIONS - ITERATIONS // 2)
-        r["fit_share"] = r["fits_us"] / r["odd_us"]
+        r["odd_us"] = {f: (r["level_ms"][f]["median"] * 1e3 - (ITERATIONS // 2) * r["even_us"]) / (ITERATIONS - ITERATIONS // 2) for f in FORMS}
+        r["fit_share"] = {f: r["fit_us"][f]["median"] / r["odd_us"][f] for f in FORMS}
         t0 = time.perf_counter()
         sr.level(PHI, D, order, sr.INVERSE, 1.5, 0.7, REF_ITERATIONS, 0.0, seed=1)
         r["ref_ms"] = (time.perf_counter() - t0) * 1e3 * ITERATIONS / REF_ITERATIONS
@@ -137,14 +170,15 @@ def _kernel_split(outdir):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--ab", type=int, default=5, help="alternations of the batched and the chained form (at least 5)")
     ap.add_argument("--child", choices=["full", "kernels"])
     a = ap.parse_args()
     if a.child:
-        print(json.dumps(_child_timing(a.reps, a.child == "kernels")))
+        print(json.dumps(_child_timing(a.reps, a.child == "kernels", max(a.ab, 5))))
         return
     res = {}
     me = os.path.abspath(__file__)
-    step = subprocess.run(["timeout", "-k", "10", "300", sys.executable, me, "--child", "full", "--reps", str(a.reps)],
+    step = subprocess.run(["timeout", "-k", "10", "300", sys.executable, me, "--child", "full", "--reps", str(a.reps), "--ab", str(a.ab)],
                           capture_output=True, text=True, cwd=ROOT)
     if step.returncode != 0:
         res["error"] = "timing step exited %d: %s" % (step.returncode, step.stderr[-400:])
