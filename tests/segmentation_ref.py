@@ -51,7 +51,7 @@ def sizes(PHI):
 
 def variance(PHI, dist, minCOV, dist_cap=np.inf):
     """(cov float64 [S], n int [S]); the sum runs over the counted pixels in column-major order (the library's fixed order
-    differs: cov agrees within 2*n*2^-53 relative)."""
+    differs: cov agrees within 2*n*2^-53 relative; variance_in_order restates that order)."""
     PHI, dist = _p3(PHI), _p3(dist)
     S = PHI.shape[2]
     cov, n = np.zeros(S), np.zeros(S, np.int64)
@@ -67,6 +67,41 @@ def variance(PHI, dist, minCOV, dist_cap=np.inf):
         with np.errstate(all="ignore"):
             c = np.float64(tot) / np.float64(v.size)
         cov[s] = minCOV if c < minCOV else c
+    return cov, n
+
+
+TILE, WAVE = 256, 64  # pixels of a tile of the library's sums, lanes of a wave
+
+
+def variance_in_order(PHI, dist, minCOV, dist_cap=np.inf):
+    """(cov float64 [S], n int [S]) with the sum taken in the order include/pdeip.h step 2c, csrc/pdeip_reduce.hpp and DESIGN 5.10
+    document, restated in NumPy's IEEE float64 additions and compared with the library BIT FOR BIT: the plane in memory
+    (column-major) order, padded with +0.0 to whole tiles of 256; a pixel's value is (double)dist where it is counted, +0.0 where
+    not; per wave of 64 the six butterfly steps v = v + v[lane ^ d], d = 32 .. 1, lane 0 taken; a tile's four waves as
+    ((w0 + w1) + w2) + w3; the tiles as t = 0.0, t = t + tile_k in ascending k; cov = t / n, then variance()'s minCOV rule."""
+    PHI, dist = _p3(PHI), _p3(dist)
+    nrows, ncols, S = PHI.shape
+    npix = nrows * ncols
+    tiles = -(-npix // TILE)
+    d = dist.transpose(2, 1, 0).reshape(S, npix).astype(np.float64)
+    m = mask(PHI).transpose(2, 1, 0).reshape(S, npix)
+    with np.errstate(all="ignore"):
+        if np.isfinite(dist_cap):
+            m = m & (d < dist_cap)
+        n = m.sum(axis=1).astype(np.int64)
+        v = np.zeros((S, tiles * TILE))
+        v[:, :npix] = np.where(m, d, 0.0)
+        v = v.reshape(S, tiles, TILE // WAVE, WAVE)
+        lane = np.arange(WAVE)
+        for step in (32, 16, 8, 4, 2, 1):
+            v = v + v[..., lane ^ step]
+        w = v[..., 0]
+        tile = ((w[:, :, 0] + w[:, :, 1]) + w[:, :, 2]) + w[:, :, 3]
+        t = np.zeros(S)
+        for k in range(tiles):
+            t = t + tile[:, k]
+        cov = t / n.astype(np.float64)
+        cov = np.where(cov < minCOV, np.float64(minCOV), cov)
     return cov, n
 
 
