@@ -1017,6 +1017,46 @@ int pdeip_disp_segmentation_sparse(const float *Din, int nrows, int ncols, const
                                    const pdeip_dispseg_params *prm, unsigned long long seed, int *S_out, float *PHI_out, int *SEG_out,
                                    float *surf_out);
 
+/* ---- flow colour coding and error measures (csrc/pdeip_flowviz.hip) -------------------------------------------------------------
+ *
+ * img = flow2color(cat(3, U, V), 'maxvalue', maxvalue, 'border', border) (matlab/optical_flow/flow2color.m), the whole function:
+ *   dir   = atan2(-V, -U), negative angles + 2 pi, / (2 pi): the hue in turns
+ *   mag   = sqrt(U^2 + V^2) / maxvalue, values above 1 set to 1
+ *   valid = isfinite(U) & (mag <= 1)   (a NaN in V makes mag NaN; an Inf in V alone leaves the pixel valid, as in the .m)
+ *   hsv   = valid ? (dir, 1, mag) : (1, 0, 1), i.e. white; rgb = hsv2rgb(hsv)
+ * maxvalue NaN stands for the .m's empty default: the maximum magnitude of the field by MATLAB's max (NaN magnitudes ignored, Inf
+ * counts, an all-NaN field gives NaN and an all-white picture; a zero field gives 0/0 and an all-white picture).  *maxvalue_out (may
+ * be NULL) receives the value used, in place of the .m's disp().
+ * border > 0: the picture is (nrows + 2 border) x (ncols + 2 border); its frame is the colour coding of X = (j / bcols - 0.5) * 10,
+ * Y = (i / brows - 0.5) * 10 (1-based i, j) normalised by its own maximum sqrt(50), and the flow's picture is pasted at 1-based
+ * index `border`, i.e. 0-based offset border - 1 (flow2color.m:66; the .m's off-by-one, kept).
+ * U, V: column-major float32 [nrows x ncols].  rgb_out: float32 [brows x bcols x 3] in MATLAB layout, or NULL.  rgb8_out: the same
+ * picture as uint8(round(255 x)), interleaved RGB in row-major order [brows][bcols][3], or NULL.  One of the two must be given.
+ * Arithmetic (this library's definition; MATLAB's hsv2rgb is not pinned): inputs promoted to float64, every step in float64 without
+ * FMA, hsv2rgb the six-sector formula (k = floor(6 h), k = 6 as 0, f = 6 h - k, p = v (1 - s), q = v (1 - s f), t = v (1 - s (1 - f))),
+ * one rounding to float32; rgb8 is computed from the float32 value.
+ * _dev: device pointers (maxvalue_out a device double), launches on `stream`, nothing read back, graph-capturable once the
+ * workspace exists; 1 launch with maxvalue given, 3 with maxvalue NaN, whatever the data (pdeip_last_launch_count()).
+ * Refused with PDEIP_ERR_ARG before any HIP call: U or V NULL, both outputs NULL, nrows or ncols < 1, border < 0, a picture of more
+ * than 2^31-1 elements; PDEIP_ERR_UNSUPPORTED: more than 1048560 columns. */
+int pdeip_flow2color_dev(void *stream, const float *U, const float *V, int nrows, int ncols, double maxvalue, int border, float *rgb_out,
+                         unsigned char *rgb8_out, double *maxvalue_out);
+int pdeip_flow2color(const float *U, const float *V, int nrows, int ncols, double maxvalue, int border, float *rgb_out,
+                     unsigned char *rgb8_out, double *maxvalue_out);
+/* The flow (U, V) against a ground truth (Ut, Vt).  A pixel counts when all four values are finite there and mask (float32
+ * [nrows x ncols], or NULL for every pixel) is nonzero.  Per counted pixel, in float64 on the promoted inputs, without FMA:
+ *   endpoint error   sqrt((U - Ut)^2 + (V - Vt)^2)
+ *   angular error    acos(clamp((U Ut + V Vt + 1) / (sqrt(U^2 + V^2 + 1) sqrt(Ut^2 + Vt^2 + 1)), -1, 1)) * (180 / pi)   (Barron et al.)
+ * epe_out, ang_out: float32 [nrows x ncols] or NULL; pixels that do not count hold NaN.  stats_out: double[4] = {count, mean
+ * endpoint error, mean angular error, largest endpoint error}; with count 0 the last three are NaN.  The sums are the library's
+ * fixed-order float64 tree (thread, wave butterfly, waves ascending, tiles ascending), so a call is reproducible to the bit.
+ * _dev: device pointers, 2 launches on `stream`, nothing read back, graph-capturable once the workspace exists.
+ * Refused with PDEIP_ERR_ARG before any HIP call: U, V, Ut, Vt or stats_out NULL, nrows or ncols < 1, more than 2^31-1 pixels. */
+int pdeip_flow_errors_dev(void *stream, const float *U, const float *V, const float *Ut, const float *Vt, const float *mask, int nrows,
+                          int ncols, float *epe_out, float *ang_out, double *stats_out);
+int pdeip_flow_errors(const float *U, const float *V, const float *Ut, const float *Vt, const float *mask, int nrows, int ncols,
+                      float *epe_out, float *ang_out, double *stats_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,6 +34,7 @@ UNITS = {
     "pdeip_segmentation.hip": ["pdeip_segmentation.hpp", "pdeip_reduce.hpp", "pdeip_seeds_plan.hpp", "pdeip_sparse_plan.hpp"],
     "pdeip_sparse.hip": ["pdeip_sparse.hpp", "pdeip_cswap.hpp", "pdeip_models.hpp", "pdeip_pointwise.hpp", "pdeip_sparse_plan.hpp", "pdeip_seeds_plan.hpp"],
     "pdeip_ccl.hip": ["pdeip_ccl.hpp", "pdeip_ccl_plan.hpp"],
+    "pdeip_flowviz.hip": ["pdeip_flowviz.hpp", "pdeip_reduce.hpp"],
 }
 # -ffp-contract=off is part of the parity contract (the reference is FMA-free C).
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]

@@ -171,6 +171,11 @@ SIGNATURES = {
     "pdeip_region_competition_sparse": [_P, _P, _I, _I, _I, _I, _I, ctypes.c_double, _F, _I, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                         ctypes.c_ulonglong, _P, _P, _P, _P, _P],
     "pdeip_disp_segmentation_sparse": [_P, _I, _I, _P, _I, _P, _P, ctypes.c_ulonglong, _P, _P, _P, _P],
+    # flow colour coding and error measures (csrc/pdeip_flowviz.hip)
+    "pdeip_flow2color_dev": [_P, _P, _P, _I, _I, ctypes.c_double, _I, _P, _P, _P],
+    "pdeip_flow2color": [_P, _P, _I, _I, ctypes.c_double, _I, _P, _P, _P],
+    "pdeip_flow_errors_dev": [_P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P],
+    "pdeip_flow_errors": [_P, _P, _P, _P, _P, _I, _I, _P, _P, _P],
     # library state
     "pdeip_set_mode": [_I],
     "pdeip_get_mode": [],

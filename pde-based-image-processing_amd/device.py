@@ -777,3 +777,51 @@ def largest_component(A, conn=8, hi=1.0, lo=0.0, out=None, num_out=None, area_ou
     capi.call("pdeip_largest_component_dev", _stream(), A.data_ptr(), nrows, ncols, int(conn), float(hi), float(lo), out.data_ptr(),
               num_out.data_ptr() if num_out is not None else None, area_out.data_ptr() if area_out is not None else None)
     return out
+
+
+# ---- flow colour coding and error measures (csrc/pdeip_flowviz.hip) ----
+def flow2color(U, V, maxvalue=None, border=0, uint8=False, out=None, maxvalue_out=None):
+    """img = flow2color(cat(3, U, V), 'maxvalue', maxvalue, 'border', border) on resident planes (pdeip_flow2color_dev): U, V
+    [ncols, nrows]; maxvalue None: the field's largest magnitude, found on the device.  Returns (img, maxvalue_out): img float32
+    [3, bcols, brows] (MATLAB's [brows, bcols, 3]; to_matlab converts) or, with uint8=True, the uint8 tensor [brows, bcols, 3] an image
+    writer takes; maxvalue_out a float64 tensor [1] holding the maximum used.  Nothing is read back."""
+    _chk(U, V)
+    if U.dim() != 2 or V.shape != U.shape:
+        raise capi.PdeipError(capi.PDEIP_ERR_ARG, "flow2color: U and V must be planes [ncols, nrows] of one shape")
+    nrows, ncols, _ = _dims(U)
+    border = int(border)
+    brows, bcols = nrows + 2 * max(border, 0), ncols + 2 * max(border, 0)
+    if out is None:
+        out = (torch.empty((brows, bcols, 3), dtype=torch.uint8, device=U.device) if uint8
+               else torch.empty((3, bcols, brows), dtype=torch.float32, device=U.device))
+    _chk_typed(out, torch.uint8 if uint8 else torch.float32, 3 * brows * bcols, "flow2color: out")
+    if maxvalue_out is None:
+        maxvalue_out = torch.empty(1, dtype=torch.float64, device=U.device)
+    _chk_typed(maxvalue_out, torch.float64, 1, "flow2color: maxvalue_out")
+    capi.call("pdeip_flow2color_dev", _stream(), U.data_ptr(), V.data_ptr(), nrows, ncols, float("nan") if maxvalue is None else float(maxvalue),
+              border, None if uint8 else out.data_ptr(), out.data_ptr() if uint8 else None, maxvalue_out.data_ptr())
+    return out, maxvalue_out
+
+
+def flow_errors(U, V, Ut, Vt, mask=None, epe_out=None, ang_out=None, stats_out=None, planes=True):
+    """Endpoint and angular error of the resident flow (U, V) against (Ut, Vt) (pdeip_flow_errors_dev); mask: a float32 plane,
+    nonzero where a pixel counts, or None.  Returns (epe, ang, stats): the two error planes like U (NaN where a pixel does not
+    count; None with planes=False) and a float64 tensor [4] = count, mean endpoint error, mean angular error in degrees, largest
+    endpoint error.  Nothing is read back."""
+    fields = (U, V, Ut, Vt) if mask is None else (U, V, Ut, Vt, mask)
+    _chk(*fields)
+    if U.dim() != 2 or any(t.shape != U.shape for t in fields):
+        raise capi.PdeipError(capi.PDEIP_ERR_ARG, "flow_errors: U, V, Ut, Vt and mask must be planes [ncols, nrows] of one shape")
+    nrows, ncols, _ = _dims(U)
+    if planes:
+        epe_out = torch.empty_like(U) if epe_out is None else epe_out
+        ang_out = torch.empty_like(U) if ang_out is None else ang_out
+    for t, what in ((epe_out, "epe_out"), (ang_out, "ang_out")):
+        if t is not None:
+            _chk_typed(t, torch.float32, nrows * ncols, "flow_errors: " + what)
+    if stats_out is None:
+        stats_out = torch.empty(4, dtype=torch.float64, device=U.device)
+    _chk_typed(stats_out, torch.float64, 4, "flow_errors: stats_out")
+    capi.call("pdeip_flow_errors_dev", _stream(), *_p(U, V, Ut, Vt), None if mask is None else mask.data_ptr(), nrows, ncols,
+              None if epe_out is None else epe_out.data_ptr(), None if ang_out is None else ang_out.data_ptr(), stats_out.data_ptr())
+    return epe_out, ang_out, stats_out

@@ -16,6 +16,7 @@ capi.MODE_RED_BLACK the parallel one).
     Diffusion4_v10              matlab/diffusion/Diffusion4_v10.m                 nonlinear diffusion (C++ only: pdeip_diffusion4)
     regionCompetition           matlab/segmentation/DispSegmentation.m:448-654    region competition of the segmentation drivers
     segments_numbered           matlab/segmentation/DispSegmentation.m:190-198    (C++ only: pdeip_region_competition, pdeip_seg_label)
+    flow2color / flow_errors    matlab/optical_flow/flow2color.m                  colour coding; error measures (C++ only: pdeip_flow2color)
 
 `Us=`, `Vs=` (param.Us / param.Vs: spatial a-priori fields, double, NaN = no constraint) and `scales=` (param.scales) are taken
 by the late-linearisation flow drivers and the disparity driver as the reference's drivers take them.
@@ -757,3 +758,51 @@ def sparse_pyramid(D, scl_factor=0.75, pyr_scl=0.55):
         planes.append(np.asfortranarray(out[at:at + r * c].reshape(c, r).T))
         at += r * c
     return planes
+
+
+def flow2color(flow, uint8=False, return_max=False, **param):
+    """img = flow2color(flow, 'maxvalue', m, 'border', b) (matlab/optical_flow/flow2color.m) in one pdeip_flow2color call: hue
+    codes the direction, intensity the magnitude over maxvalue (default: the field's largest magnitude), invalid pixels are white;
+    border > 0 adds the direction frame, the flow's picture pasted at the .m's offset border - 1.  flow [rows, cols, 2] in any numeric
+    type, taken as single(flow).  Returns the single picture [rows + 2 b, cols + 2 b, 3], or with uint8=True uint8(round(255 img)) as
+    [rows + 2 b, cols + 2 b, 3] in C order; with return_max=True, (img, maxvalue), the maximum the .m displays."""
+    for k in param:
+        if k not in ("maxvalue", "border"):
+            raise TypeError("flow2color: unknown parameter %r" % k)
+    F = np.asarray(flow, dtype=np.float32)
+    if F.ndim != 3 or F.shape[2] != 2:
+        raise ValueError("flow2color: flow must be [rows, cols, 2] (got %s)" % (F.shape,))
+    maxvalue, border = param.get("maxvalue"), param.get("border", 0)
+    if maxvalue is not None and np.size(maxvalue) == 0:
+        maxvalue = None  # the .m's empty default
+    if border != int(border) or border < 0:
+        raise ValueError("flow2color: border must be a non-negative integer (got %r)" % (border,))
+    border = int(border)
+    U, V = np.asfortranarray(F[:, :, 0]), np.asfortranarray(F[:, :, 1])
+    rows, cols = U.shape
+    brows, bcols = rows + 2 * border, cols + 2 * border
+    img = np.empty((brows, bcols, 3), np.uint8) if uint8 else np.empty((brows, bcols, 3), np.float32, order="F")
+    used = ctypes.c_double(0.0)
+    capi.call("pdeip_flow2color", U.ctypes.data, V.ctypes.data, rows, cols, math.nan if maxvalue is None else float(maxvalue), border,
+              None if uint8 else img.ctypes.data, img.ctypes.data if uint8 else None, ctypes.addressof(used))
+    return (img, used.value) if return_max else img
+
+
+def flow_errors(U, V, Utrue, Vtrue, mask=None):
+    """The flow (U, V) against the ground truth in one pdeip_flow_errors call.  A pixel counts when the four values are finite and
+    mask (nonzero = counts; None: every pixel) allows it.  Returns a dict: epe and ang, the endpoint and Barron's angular error
+    (degrees) as single planes with NaN where a pixel does not count; count, mean_epe, mean_ang, max_epe."""
+    planes = [np.asfortranarray(np.asarray(a, dtype=np.float32)) for a in (U, V, Utrue, Vtrue)]
+    if planes[0].ndim != 2 or any(p.shape != planes[0].shape for p in planes):
+        raise ValueError("flow_errors: U, V, Utrue and Vtrue must be [rows, cols] arrays of one shape")
+    m = None
+    if mask is not None:
+        m = np.asfortranarray(np.asarray(mask, dtype=np.float32))
+        if m.shape != planes[0].shape:
+            raise ValueError("flow_errors: mask must have the flow's shape")
+    rows, cols = planes[0].shape
+    epe, ang = np.empty((rows, cols), np.float32, order="F"), np.empty((rows, cols), np.float32, order="F")
+    stats = (ctypes.c_double * 4)()
+    capi.call("pdeip_flow_errors", *[p.ctypes.data for p in planes], None if m is None else m.ctypes.data, rows, cols, epe.ctypes.data,
+              ang.ctypes.data, ctypes.addressof(stats))
+    return dict(epe=epe, ang=ang, count=int(stats[0]), mean_epe=stats[1], mean_ang=stats[2], max_epe=stats[3])

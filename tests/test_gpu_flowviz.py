@@ -1,0 +1,471 @@
+"""GPU: pdeip_flow2color(_dev) and pdeip_flow_errors(_dev) against the restatement (flowviz_ref.py, pinned by test_flowviz_ref.py).
+
+Every case runs on planes carved at a 4-byte offset as well as on 16-byte aligned ones (the maximum's kernel loads float4 only from
+aligned planes).  Shapes: single lanes, rows and columns each side of a wave (64), a 16 x 16 tile and a workgroup (256), many
+workgroups.  Fields: a seeded normal flow; the same laced with NaN in U only, in V only, with +-Inf in U, in V -- at the first pixel,
+the last pixel and the workgroup seams, nowhere else; -0.0 components; the all-zero and the all-NaN field.
+
+  maxvalue_out   bit for bit (a maximum is exact)
+  float rgb      |gpu - ref| <= 2^-24: both sides evaluate in float64 to far better than 2^-40, so the one rounding to float32 of a
+                 value in [0, 1] differs by at most one ulp, at most 2^-24; exactly equal on invalid and zero-magnitude pixels
+  uint8          round(255 ref); 1 off only where 255 ref is within 255 * 2^-24 of a half-integer
+  errors         the endpoint error plane, the count and the largest endpoint error bit for bit (correctly rounded IEEE operations on
+                 identical inputs); the mean endpoint error within 2 n 2^-53 relative of math.fsum (two summation orders of
+                 non-negative terms); the angular error within ANG_TOL relative (only the two libraries' acos differ)
+"""
+import importlib
+import math
+
+import numpy as np
+import pytest
+
+import flowviz_ref as fr
+
+pytestmark = pytest.mark.gpu
+F32, F64 = np.float32, np.float64
+
+SHAPES = [(1, 1), (1, 7), (7, 1), (5, 300), (257, 3), (37, 53), (270, 480)]
+FIELDS = ["normal", "nan_u", "nan_v", "inf_u", "inf_v", "neg_zero", "zero", "all_nan"]
+RGB_TOL = 2.0 ** -24
+# The relative difference between the device's double acos and the host libm's, argument identical.  No ulp statement for the device
+# math library ships with the toolchain, so the figure was measured once on the MI355X (23 205 pixels of these cases'
+# fields, random, nearly parallel and nearly opposite pairs, each pixel's float64 value read through a one-pixel mask): 2.48e-16 =
+# 2^-51.84, a little over one ulp.  The bound is four times that (another libm version has to pass too), never looser than 2^-40.
+ANG_MEASURED = 2.48e-16
+ANG_TOL = min(4.0 * ANG_MEASURED, 2.0 ** -40)
+
+
+def _dev():
+    return importlib.import_module("pde-based-image-processing_amd.device")
+
+
+def _drv():
+    return importlib.import_module("pde-based-image-processing_amd.drivers")
+
+
+def lace_positions(shape):
+    """Column-major linear indices: the first pixel, the last, both sides of a 256-pixel workgroup seam and of the 1024-pixel seam of
+    the float4 path, and the corners where four 16 x 16 tiles meet."""
+    rows, cols = shape
+    n = rows * cols
+    at = {0, n - 1, 255, 256, 1023, 1024}
+    if rows > 16 and cols > 16:
+        at |= {15 * rows + 15, 16 * rows + 16}
+    return sorted(k for k in at if 0 <= k < n)
+
+
+def field(shape, kind, seed=11):
+    rng = np.random.default_rng(seed + 1000 * shape[0] + shape[1])
+    U = np.asfortranarray((3.0 * rng.normal(size=shape)).astype(F32))
+    V = np.asfortranarray((3.0 * rng.normal(size=shape)).astype(F32))
+    u, v = U.reshape(-1, order="F"), V.reshape(-1, order="F")   # views
+    at = lace_positions(shape)
+    if kind == "nan_u":
+        u[at] = np.nan
+    elif kind == "nan_v":
+        v[at] = np.nan
+    elif kind == "inf_u":
+        u[at] = [np.inf if k % 2 == 0 else -np.inf for k in range(len(at))]
+    elif kind == "inf_v":
+        v[at] = [-np.inf if k % 2 == 0 else np.inf for k in range(len(at))]
+    elif kind == "neg_zero":
+        for k, p in enumerate(at):
+            if k % 3 != 1:
+                u[p] = -0.0
+            if k % 3 != 0:
+                v[p] = -0.0 if k % 2 else 0.0
+    elif kind == "zero":
+        U[...] = 0.0
+        V[...] = 0.0
+    elif kind == "all_nan":
+        U[...] = np.nan
+        V[...] = np.nan
+    return U, V
+
+
+def carve(a, offset):
+    """The plane on the device, [ncols, nrows]; offset 1: at 4 bytes past a 16-byte boundary."""
+    import torch
+
+    t = _dev().to_device(a)
+    if not offset:
+        assert t.data_ptr() % 16 == 0
+        return t
+    buf = torch.empty(t.numel() + 4, dtype=torch.float32, device=t.device)
+    assert buf.data_ptr() % 16 == 0
+    out = buf[1:1 + t.numel()].view(t.shape)
+    out.copy_(t)
+    assert out.data_ptr() % 16 == 4 and out.is_contiguous()
+    return out
+
+
+def _bits(x):
+    return np.float64(x).view(np.uint64)
+
+
+def _same_max(got, want, what):
+    assert (math.isnan(got) and math.isnan(want)) or _bits(got) == _bits(want), "%s: maxvalue %r != %r" % (what, got, want)
+
+
+def check_rgb(got, ref32, exact, what):
+    assert got.shape == ref32.shape and got.dtype == F32, what
+    diff = np.abs(got.astype(F64) - ref32.astype(F64))
+    assert not np.isnan(diff).any() and diff.max() <= RGB_TOL, "%s: float rgb off by %.3g" % (what, diff.max())
+    assert np.array_equal(got[exact], ref32[exact]), "%s: invalid / zero-magnitude pixels differ" % what
+
+
+def check_u8(got, ref32, ref64, what):
+    want = fr.to_uint8(ref32)
+    assert got.shape == want.shape and got.dtype == np.uint8, what
+    off = got != want
+    if off.any():
+        y = 255.0 * ref64[off]
+        assert np.all(np.abs(got[off].astype(np.int64) - want[off].astype(np.int64)) == 1), what
+        assert np.all(np.abs(y - (np.floor(y) + 0.5)) <= 255.0 * RGB_TOL), "%s: uint8 differs away from a half-integer" % what
+
+
+def exact_mask(U, V, valid, border=0):
+    """Pixels of the picture that must match to the bit: the flow's invalid and zero-magnitude ones."""
+    inner = ~valid | ((U == 0) & (V == 0))
+    rows, cols = U.shape
+    m = np.zeros((rows + 2 * border, cols + 2 * border), bool)
+    o = max(border - 1, 0)
+    m[o:o + rows, o:o + cols] = inner
+    return m
+
+
+def run_color(pdeip, U, V, offset, maxvalue=None, border=0):
+    """Both outputs of the _dev form, the maximum and the launch counts."""
+    import torch
+
+    dev = _dev()
+    tU, tV = carve(U, offset), carve(V, offset)
+    img, mv = dev.flow2color(tU, tV, maxvalue=maxvalue, border=border)
+    n1 = pdeip.capi.load().pdeip_last_launch_count()
+    img8, mv8 = dev.flow2color(tU, tV, maxvalue=maxvalue, border=border, uint8=True)
+    n2 = pdeip.capi.load().pdeip_last_launch_count()
+    torch.cuda.synchronize()
+    assert pdeip.capi.last_error() == ""
+    assert dev.to_matlab(tU).tobytes() == U.tobytes() and dev.to_matlab(tV).tobytes() == V.tobytes(), "the input was modified"
+    assert n1 == n2 == (3 if maxvalue is None else 1)
+    _same_max(float(mv8.cpu()[0]), float(mv.cpu()[0]), "uint8 call")
+    return dev.to_matlab(img), img8.cpu().numpy(), float(mv.cpu()[0])
+
+
+@pytest.mark.parametrize("kind", FIELDS)
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "%dx%d" % s)
+def test_flow2color_equals_the_restatement(pdeip, shape, kind):
+    U, V = field(shape, kind)
+    ref32, rmax, ref64, valid = fr.flow2color(U, V, detail=True)
+    given = 2.5
+    g32, gmax, g64, gvalid = fr.flow2color(U, V, maxvalue=given, detail=True)
+    for offset in (0, 1):
+        what = "%s %s offset %d" % (shape, kind, offset)
+        img, img8, mv = run_color(pdeip, U, V, offset)
+        _same_max(mv, rmax, what)
+        check_rgb(img, ref32, exact_mask(U, V, valid), what)
+        check_u8(img8, ref32, ref64, what)
+        # maxvalue given: one launch, the data's own maximum plays no part
+        img, img8, mv = run_color(pdeip, U, V, offset, maxvalue=given)
+        assert mv == given
+        check_rgb(img, g32, exact_mask(U, V, gvalid), what + " maxvalue given")
+        check_u8(img8, g32, g64, what + " maxvalue given")
+    if kind in ("zero", "all_nan"):   # white under the automatic maximum (0 / 0, NaN); given one, a zero field is black
+        assert np.all(ref32 == 1.0) and np.all(img8 == (255 if kind == "all_nan" else 0))
+
+
+def test_given_maxvalue_ignores_the_largest_pixel(pdeip):
+    U, V = field((37, 53), "normal")
+    a, _, _ = run_color(pdeip, U, V, 1, maxvalue=4.0)
+    U2 = U.copy(order="F")
+    U2[20, 30] = 1e6
+    b, _, _ = run_color(pdeip, U2, V, 1, maxvalue=4.0)
+    same = np.ones(U.shape, bool)
+    same[20, 30] = False
+    assert a[same].tobytes() == b[same].tobytes()
+    c, _, mv = run_color(pdeip, U2, V, 1)
+    assert mv == fr.max_magnitude(U2, V) and not np.array_equal(a[same], c[same])
+
+
+def test_host_form_and_uint8_layout(pdeip):
+    """The host form equals the _dev form byte for byte; the uint8 picture is [rows][cols][3] on a non-square case."""
+    drv = _drv()
+    for kind in ("normal", "nan_v", "inf_u"):
+        U, V = field((37, 53), kind)
+        flow = np.stack([U, V], axis=2)
+        for border, maxvalue in ((0, None), (2, None), (0, 2.5)):
+            param = dict(border=border) if maxvalue is None else dict(border=border, maxvalue=maxvalue)
+            img, mv = drv.flow2color(flow, return_max=True, **param)
+            assert pdeip.capi.last_error() == ""
+            img8, mv8 = drv.flow2color(flow, uint8=True, return_max=True, **param)
+            d32, d8, dmv = run_color(pdeip, U, V, 0, maxvalue=maxvalue, border=border)
+            assert img.tobytes() == d32.tobytes() and img8.tobytes() == d8.tobytes()
+            _same_max(mv, dmv, kind)
+            _same_max(mv8, dmv, kind)
+            assert img.shape == (37 + 2 * border, 53 + 2 * border, 3) and img8.shape == img.shape and img8.flags.c_contiguous
+            # pixel (i, j) of the interleaved row-major picture is the rounding of the float picture's pixel (i, j)
+            assert np.array_equal(img8, fr.to_uint8(img))
+            flat = np.frombuffer(img8.tobytes(), np.uint8)
+            i, j = 5, 40
+            assert list(flat[(i * img.shape[1] + j) * 3:(i * img.shape[1] + j) * 3 + 3]) == list(fr.to_uint8(img[i, j, :]))
+
+
+@pytest.mark.parametrize("border", [1, 2, 10])
+def test_border_frame_and_paste_offset(pdeip, border):
+    for kind in ("normal", "nan_u"):
+        U, V = field((37, 53), kind)
+        ref32, rmax, ref64, valid = fr.flow2color(U, V, border=border, detail=True)
+        for offset in (0, 1):
+            what = "border %d %s offset %d" % (border, kind, offset)
+            plain, plain8, _ = run_color(pdeip, U, V, offset)
+            img, img8, mv = run_color(pdeip, U, V, offset, border=border)
+            _same_max(mv, rmax, what)
+            assert img.shape == (37 + 2 * border, 53 + 2 * border, 3)
+            check_rgb(img, ref32, exact_mask(U, V, valid, border), what)   # frame pixels included
+            check_u8(img8, ref32, ref64, what)
+            o = border - 1
+            assert img[o:o + 37, o:o + 53, :].tobytes() == plain.tobytes(), what + ": the interior is not the border = 0 picture"
+            assert img8[o:o + 37, o:o + 53, :].tobytes() == plain8.tobytes()
+
+
+# ---- error measures ----
+def truth(shape, kind):
+    Ut, Vt = field(shape, "normal", seed=23)
+    if kind in ("nan_u", "inf_u"):   # a non-finite truth pixel too, next to the laced ones
+        Vt.reshape(-1, order="F")[[k for k in (1, 257) if k < Vt.size]] = np.nan if kind == "nan_u" else np.inf
+    return Ut, Vt
+
+
+def mask_for(shape, kind):
+    rng = np.random.default_rng(31 + shape[0])
+    m = np.asfortranarray((rng.random(shape) < 0.7).astype(F32) * F32(2.0))
+    f = m.reshape(-1, order="F")
+    if f.size > 3:
+        f[2] = -0.0        # a zero
+        f[3] = np.nan      # nonzero
+    return m
+
+
+def ulp_mid_ok(got32, ref32, ref64, tol, what):
+    """got32 equals ref32 up to the one float32 rounding: where they differ they are neighbours and the float64 value lies within
+    tol (relative) of the midpoint between them."""
+    off = got32 != ref32
+    off &= ~(np.isnan(got32) & np.isnan(ref32))
+    if off.any():
+        g, r, x = got32[off].astype(F64), ref32[off].astype(F64), ref64[off]
+        assert np.all(np.abs(g - r) <= np.spacing(np.maximum(np.abs(got32[off]), np.abs(ref32[off]))).astype(F64)), what + ": not neighbours"
+        assert np.all(np.abs(x - 0.5 * (g + r)) <= tol * np.abs(x)), what + ": differs away from a rounding boundary"
+
+
+def run_errors(pdeip, planes, mask, offset):
+    import torch
+
+    dev = _dev()
+    ts = [carve(p, offset) for p in planes]
+    tm = None if mask is None else carve(mask, offset)
+    epe, ang, stats = dev.flow_errors(*ts, mask=tm)
+    assert pdeip.capi.load().pdeip_last_launch_count() == 2
+    epe2, ang2, stats2 = dev.flow_errors(*ts, mask=tm, epe_out=torch.full_like(ts[0], 5.0), ang_out=torch.full_like(ts[0], 5.0))
+    torch.cuda.synchronize()
+    assert pdeip.capi.last_error() == ""
+    out = dev.to_matlab(epe), dev.to_matlab(ang), stats.cpu().numpy()
+    assert dev.to_matlab(epe2).tobytes() == out[0].tobytes() and dev.to_matlab(ang2).tobytes() == out[1].tobytes()
+    assert stats2.cpu().numpy().tobytes() == out[2].tobytes(), "two calls differ"
+    return out
+
+
+def check_errors(got, want, what):
+    epe, ang, stats = got
+    n = want["count"]
+    assert np.array_equal(np.isnan(epe), ~want["counted"]) and np.array_equal(np.isnan(ang), ~want["counted"]), what + ": excluded pixels differ"
+    ok = want["counted"]
+    assert np.array_equal(epe[ok].view(np.uint32), want["epe"][ok].view(np.uint32)), what + ": endpoint error bits differ"
+    assert stats[0] == n, what
+    if n == 0:
+        assert np.isnan(stats[1:]).all(), what
+        return
+    assert _bits(stats[3]) == _bits(want["max_epe"]), what
+    bound = 2.0 * n * 2.0 ** -53
+    rel_e = abs(stats[1] - want["mean_epe"]) / want["mean_epe"] if want["mean_epe"] else abs(stats[1])
+    rel_a = abs(stats[2] - want["mean_ang"]) / want["mean_ang"] if want["mean_ang"] else abs(stats[2])
+    print("%s: n %d, mean endpoint error off by %.3g relative (bound %.3g), mean angular error by %.3g (bound %.3g)"
+          % (what, n, rel_e, bound, rel_a, bound + ANG_TOL))
+    assert rel_e <= bound
+    assert rel_a <= bound + ANG_TOL
+    ulp_mid_ok(ang, want["ang"], want["ang_plane64"], ANG_TOL, what + " angular error")
+
+
+@pytest.mark.parametrize("kind", ["normal", "nan_u", "nan_v", "inf_u", "inf_v", "neg_zero"])
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "%dx%d" % s)
+def test_flow_errors_equal_the_restatement(pdeip, shape, kind):
+    U, V = field(shape, kind)
+    Ut, Vt = truth(shape, kind)
+    mask = mask_for(shape, kind)
+    for offset in (0, 1):
+        for m in (None, mask):
+            what = "%s %s offset %d%s" % (shape, kind, offset, "" if m is None else " masked")
+            check_errors(run_errors(pdeip, (U, V, Ut, Vt), m, offset), fr.flow_errors(U, V, Ut, Vt, m), what)
+
+
+def test_flow_errors_single_pixels_in_double(pdeip):
+    """A mask of one pixel makes the mean angular error that pixel's float64 value (0 + x is exact): the device's acos against the
+    host's directly, within ANG_TOL relative; identical fields give 0."""
+    import torch
+
+    dev = _dev()
+    shape = (37, 53)
+    U, V = field(shape, "normal")
+    Ut, Vt = truth(shape, "normal")
+    want = fr.flow_errors(U, V, Ut, Vt)
+    ts = [dev.to_device(p) for p in (U, V, Ut, Vt)]
+    mask = torch.zeros_like(ts[0])
+    worst = 0.0
+    for k in range(0, U.size, 61):
+        j, i = divmod(k, shape[0])
+        mask.zero_()
+        mask[j, i] = 1.0
+        _, _, stats = dev.flow_errors(*ts, mask=mask, planes=False)
+        s = stats.cpu().numpy()
+        x = want["ang_plane64"][i, j]
+        assert s[0] == 1 and _bits(s[1]) == _bits(s[3])
+        worst = max(worst, abs(s[2] - x) / x)
+    print("largest relative acos difference over %d pixels: %.3g = 2^%.2f (ANG_TOL %.3g)"
+          % (len(range(0, U.size, 61)), worst, math.log2(worst) if worst else -math.inf, ANG_TOL))
+    assert worst <= ANG_TOL
+    _, _, stats = dev.flow_errors(ts[0], ts[1], ts[0], ts[1], planes=False)
+    s = stats.cpu().numpy()
+    assert s[0] == U.size and s[1] == 0.0 and s[3] == 0.0 and 0.0 <= s[2] <= math.degrees(math.sqrt(2.0 ** -52))
+
+
+def test_flow_errors_without_a_counted_pixel(pdeip):
+    U, V = field((37, 53), "all_nan")
+    Ut, Vt = truth((37, 53), "normal")
+    epe, ang, stats = run_errors(pdeip, (U, V, Ut, Vt), None, 1)
+    assert stats[0] == 0 and np.isnan(stats[1:]).all() and np.isnan(epe).all() and np.isnan(ang).all()
+    U, V = field((5, 300), "normal")
+    Ut, Vt = truth((5, 300), "normal")
+    epe, ang, stats = run_errors(pdeip, (U, V, Ut, Vt), np.zeros((5, 300), F32, order="F"), 0)
+    assert stats[0] == 0 and np.isnan(stats[1:]).all() and np.isnan(epe).all()
+
+
+def test_flow_errors_host_form(pdeip):
+    U, V = field((37, 53), "nan_v")
+    Ut, Vt = truth((37, 53), "nan_u")
+    mask = mask_for((37, 53), "normal")
+    got = _drv().flow_errors(U, V, Ut, Vt, mask)
+    assert pdeip.capi.last_error() == ""
+    epe, ang, stats = run_errors(pdeip, (U, V, Ut, Vt), mask, 0)
+    assert got["epe"].tobytes() == epe.tobytes() and got["ang"].tobytes() == ang.tobytes()
+    assert np.array([got["count"], got["mean_epe"], got["mean_ang"], got["max_epe"]], F64).tobytes() == stats.tobytes()
+
+
+def test_yosemite_resident_flow_is_scored_on_the_device(pdeip, oracle):
+    """The late-linearisation flow of tests/test_yosemite.py, left on the device by its last level, scored there: the means of
+    test_yosemite._errors (handed the float32 fields promoted to float64, see test_flowviz_ref.py) within 2 n 2^-53 relative, and
+    below that file's bounds."""
+    import torch
+
+    import test_yosemite as ty
+
+    dev = _dev()
+    fl = importlib.import_module("pde-based-image-processing_amd.flow_level")
+    py = importlib.import_module("pde-based-image-processing_amd.pyramid")
+    I0, I1, Ut, Vt = ty._data()
+    P0, P1 = py.build(I0, I1)
+    level = fl.FlowLlinLevel(ty.PARAM, mode=pdeip.MODE_EXACT_ORDER)
+    resident = {}
+
+    def run_level(a, b, U, V):
+        gU, gV = level.run(dev.to_device(a), dev.to_device(b), dev.to_device(U), dev.to_device(V))
+        resident["U"], resident["V"] = gU, gV
+        return dev.to_matlab(gU), dev.to_matlab(gV)
+
+    U, V = py.coarse_to_fine(P0, P1, run_level)
+    gU, gV = resident["U"].contiguous(), resident["V"].contiguous()
+    assert dev.to_matlab(gU).tobytes() == U.tobytes()
+    tUt, tVt = dev.to_device(Ut), dev.to_device(Vt)
+    want_all, want_land = ty._errors(*[a.astype(F64) for a in (U, V, Ut, Vt)])
+    n = U.size
+    _, _, stats = dev.flow_errors(gU, gV, tUt, tVt, planes=False)
+    mask = np.zeros(U.shape, F32)
+    mask[90:, :] = 1.0
+    _, _, land = dev.flow_errors(gU, gV, tUt, tVt, mask=dev.to_device(mask), planes=False)
+    torch.cuda.synchronize()
+    stats, land = stats.cpu().numpy(), land.cpu().numpy()
+    print("all pixels: device %.17g, _errors %.17g; rows 90 on: device %.17g, _errors %.17g" % (stats[1], want_all, land[1], want_land))
+    assert stats[0] == n and land[0] == (U.shape[0] - 90) * U.shape[1]
+    assert abs(stats[1] - want_all) <= 2.0 * n * 2.0 ** -53 * want_all
+    assert abs(land[1] - want_land) <= 2.0 * n * 2.0 ** -53 * want_land
+    assert land[1] < 0.2 and stats[1] < 0.5
+    # and its picture, with runme.m's border, against the restatement
+    img, mv = dev.flow2color(gU, gV, border=10)
+    ref32, rmax, ref64, valid = fr.flow2color(U, V, border=10, detail=True)
+    _same_max(float(mv.cpu()[0]), rmax, "yosemite")
+    check_rgb(dev.to_matlab(img), ref32, exact_mask(U, V, valid, 10), "yosemite")
+
+
+def test_captured_in_a_graph(pdeip):
+    """flow2color_dev (automatic maximum, both outputs) and flow_errors_dev in one captured graph on the default queues; replayed
+    on changed inputs it equals the eager calls bit for bit."""
+    import torch
+
+    dev = _dev()
+    shape = (270, 480)
+    fields = [field(shape, "normal"), field(shape, "nan_u", seed=5), field(shape, "inf_v", seed=7)]
+    Ut, Vt = truth(shape, "normal")
+    tU, tV, tUt, tVt = [dev.to_device(p) for p in (*fields[0], Ut, Vt)]
+
+    def fresh():
+        return dict(img=torch.zeros((3, shape[1] + 4, shape[0] + 4), dtype=torch.float32, device="cuda"),
+                    img8=torch.zeros((shape[0] + 4, shape[1] + 4, 3), dtype=torch.uint8, device="cuda"),
+                    mv=torch.zeros(1, dtype=torch.float64, device="cuda"), mv8=torch.zeros(1, dtype=torch.float64, device="cuda"),
+                    epe=torch.zeros_like(tU), ang=torch.zeros_like(tU), stats=torch.zeros(4, dtype=torch.float64, device="cuda"))
+
+    def enqueue(o):
+        dev.flow2color(tU, tV, border=2, out=o["img"], maxvalue_out=o["mv"])
+        dev.flow2color(tU, tV, border=2, uint8=True, out=o["img8"], maxvalue_out=o["mv8"])
+        dev.flow_errors(tU, tV, tUt, tVt, epe_out=o["epe"], ang_out=o["ang"], stats_out=o["stats"])
+
+    cap = fresh()
+    enqueue(cap)   # the workspace exists before the capture
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=side):
+        enqueue(cap)
+    torch.cuda.current_stream().wait_stream(side)
+    for U, V in (fields[1], fields[2]):
+        tU.copy_(dev.to_device(U))
+        tV.copy_(dev.to_device(V))
+        for t in cap.values():
+            t.fill_(7)   # the replay must write everything
+        graph.replay()
+        torch.cuda.synchronize()
+        eager = fresh()
+        enqueue(eager)
+        torch.cuda.synchronize()
+        for k in cap:
+            assert cap[k].cpu().numpy().tobytes() == eager[k].cpu().numpy().tobytes(), "replay differs from the eager call in " + k
+        _same_max(float(cap["mv"].cpu()[0]), fr.max_magnitude(U, V), "replay")
+
+
+def test_stub_returns_the_drivers_picture(pdeip):
+    """flow2color_gpu through the mock MEX runtime, as matlab/flow2color_gpu.m calls it: single and double input."""
+    from test_flowviz_stub import build_flow_stub, call_typed
+
+    lib = build_flow_stub("flow2color_gpu", pdeip)
+    U, V = field((37, 53), "nan_u")
+    flow = np.asfortranarray(np.stack([U, V], axis=2))
+    for border, maxvalue in ((10, None), (0, 2.5)):
+        param = dict(border=border) if maxvalue is None else dict(border=border, maxvalue=maxvalue)
+        want, wmax = _drv().flow2color(flow, return_max=True, **param)
+        pv = np.array([np.nan if maxvalue is None else maxvalue, float(border)])
+        for f in (flow, flow.astype(F64)):
+            err, outs = call_typed(lib, (np.float32, np.float64), [f, pv])
+            assert err is None
+            assert outs[0].shape == want.shape and outs[0].tobytes(order="F") == want.tobytes(order="F")
+            assert outs[1].shape == (1, 1)
+            _same_max(float(outs[1][0, 0]), wmax, "stub")
+        err, outs = call_typed(lib, (np.float32,), [flow, pv])   # img alone
+        assert err is None and outs[0].tobytes(order="F") == want.tobytes(order="F")
