@@ -1057,6 +1057,51 @@ int pdeip_flow_errors_dev(void *stream, const float *U, const float *V, const fl
 int pdeip_flow_errors(const float *U, const float *V, const float *Ut, const float *Vt, const float *mask, int nrows, int ncols,
                       float *epe_out, float *ang_out, double *stats_out);
 
+/* ---- cross-checks: where a disparity or a flow can be trusted (csrc/pdeip_crosscheck.hip) ----------------------------------------
+ *
+ * This library's own definitions (the reference has no such function).  All arithmetic is float64 on the promoted float32 inputs,
+ * every product and sum rounded, no FMA; results are rounded once to float32.
+ *
+ * The left-right check of two disparities.  D0 is the view being checked, D1 the other view, both column-major float32
+ * [nrows x ncols] in the sign convention of the symmetric driver (pdeip_disp_nd_llin_sym): view 0's pixel x matches view 1 at
+ * x + D0(x).  Per pixel:
+ *   w    = the value pdeip_sym_warp_flow_dev(U = D1, Uq = D0) defines, bit for bit (one device function serves both): linear along
+ *          x, NaN outside 1 <= xq <= ncols, xq == ncols the last column itself; a tap with weight 0 still propagates its NaN (0 * NaN)
+ *   r    = D0 + w
+ *   kept = isfinite(r) && |r| <= tol
+ * sparse_out: kept ? D0 : NaN, D0's own bits (-0.0 included); may be D0 itself, since a thread reads only its own pixel of D0.
+ * mask_out: 1.0f or 0.0f.  diff_out: (float)r.  stats_out: double[4] = {kept, defined (pixels with finite r), mean |r| over the
+ * defined pixels, largest |r| over them}; with nothing defined the last two are NaN.  Each output may be NULL, but not all of them.
+ *
+ * The forward-backward check of two flows.  (Uf, Vf) is the flow of frame 0 -> 1, (Ub, Vb) that of frame 1 -> 0, in the flow drivers'
+ * convention (BilinInterp_2d(I1, X+U, Y+V)).  Per pixel (i, j), 0-based:
+ *   xq = (j+1) + Uf, yq = (i+1) + Vf; in range iff 1 <= xq <= ncols and 1 <= yq <= nrows, otherwise ub = vb = NaN
+ *   j0 = min(floor(xq), ncols-1), s = xq - j0; i0 = min(floor(yq), nrows-1), t = yq - i0; the +1 taps clamped to the last column / row
+ *   B(A) = (A[i0,j0] (1-s) + A[i0,j0+1] s) (1-t) + (A[i0+1,j0] (1-s) + A[i0+1,j0+1] s) t, evaluated in exactly this order
+ *   ub = B(Ub), vb = B(Vb), ru = Uf + ub, rv = Vf + vb
+ *   e    = ru ru + rv rv
+ *   lim  = a ((Uf Uf + Vf Vf) + (ub ub + vb vb)) + b
+ *   kept = isfinite(e) && e <= lim
+ * the criterion of Sundaram, Brox and Keutzer (ECCV 2010), who use a = 0.01, b = 0.5; a = 0 makes it an absolute threshold.
+ * mask_out: 1.0f or 0.0f.  err_out: (float)sqrt(e).  stats_out as above with sqrt(e) in place of |r| (defined: finite e).
+ *
+ * The statistics are the library's fixed-order float64 tree (thread, wave butterfly, waves ascending, workgroups by a strided
+ * fold and the same tree), so a call is reproducible to the bit; the counts are integers held in doubles, exact for any plane.
+ * _dev: device pointers (stats_out a device double[4]), launches on `stream`, nothing read back, graph-capturable once the
+ * workspace exists; 2 launches with stats_out, 1 without, whatever the data (pdeip_last_launch_count()).  The inputs are never
+ * written.  Planes may start at any 4-byte offset.
+ * Refused with PDEIP_ERR_ARG before any HIP call: a NULL input, every output NULL, ncols < 2 (the flow call: nrows < 2 as well),
+ * nrows < 1, more than 2^31-1 pixels, tol, a or b NaN or negative (+Inf is allowed), an output pointer equal to a gathered plane
+ * (D1, Ub, Vb); PDEIP_ERR_UNSUPPORTED: more than 65535 columns. */
+int pdeip_disp_crosscheck_dev(void *stream, const float *D0, const float *D1, int nrows, int ncols, double tol, float *sparse_out,
+                              float *mask_out, float *diff_out, double *stats_out);
+int pdeip_disp_crosscheck(const float *D0, const float *D1, int nrows, int ncols, double tol, float *sparse_out, float *mask_out,
+                          float *diff_out, double *stats_out);
+int pdeip_flow_crosscheck_dev(void *stream, const float *Uf, const float *Vf, const float *Ub, const float *Vb, int nrows, int ncols,
+                              double a, double b, float *mask_out, float *err_out, double *stats_out);
+int pdeip_flow_crosscheck(const float *Uf, const float *Vf, const float *Ub, const float *Vb, int nrows, int ncols, double a, double b,
+                          float *mask_out, float *err_out, double *stats_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,7 +23,7 @@ UNITS = {
     "pdeip_walk5.hip": ["pdeip_models.hpp", "pdeip_sor_exact.hpp", "pdeip_walk_host.hpp", "pdeip_sor_walk.hpp"],
     "pdeip_sor9.hip": ["pdeip_models.hpp", "pdeip_pointwise.hpp", "pdeip_sor_pde8.hpp", "pdeip_sor_pde8_persist.hpp", "pdeip_sor_exact.hpp", "pdeip_sor_rb.hpp", "pdeip_persist_host.hpp", "pdeip_sor_small.hpp", "pdeip_sor_plan.hpp"],
     "pdeip_line.hip": ["pdeip_alr.hpp", "pdeip_alr_plan.hpp", "pdeip_models.hpp"],
-    "pdeip_stages.hip": ["pdeip_models.hpp", "pdeip_pointwise.hpp", "pdeip_flow.hpp", "pdeip_cswap.hpp", "pdeip_fas.hpp", "pdeip_sym.hpp", "pdeip_pyr.hpp",
+    "pdeip_stages.hip": ["pdeip_models.hpp", "pdeip_pointwise.hpp", "pdeip_flow.hpp", "pdeip_cswap.hpp", "pdeip_fas.hpp", "pdeip_sym.hpp", "pdeip_sym_warp.hpp", "pdeip_pyr.hpp",
                          "pdeip_tv.hpp"],
     "pdeip_host.hip": [],
     "pdeip_drivers.hip": [],
@@ -35,6 +35,7 @@ UNITS = {
     "pdeip_sparse.hip": ["pdeip_sparse.hpp", "pdeip_cswap.hpp", "pdeip_models.hpp", "pdeip_pointwise.hpp", "pdeip_sparse_plan.hpp", "pdeip_seeds_plan.hpp"],
     "pdeip_ccl.hip": ["pdeip_ccl.hpp", "pdeip_ccl_plan.hpp"],
     "pdeip_flowviz.hip": ["pdeip_flowviz.hpp", "pdeip_reduce.hpp"],
+    "pdeip_crosscheck.hip": ["pdeip_crosscheck.hpp", "pdeip_sym_warp.hpp", "pdeip_reduce.hpp"],
 }
 # -ffp-contract=off is part of the parity contract (the reference is FMA-free C).
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]

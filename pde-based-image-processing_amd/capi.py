@@ -176,6 +176,11 @@ SIGNATURES = {
     "pdeip_flow2color": [_P, _P, _I, _I, ctypes.c_double, _I, _P, _P, _P],
     "pdeip_flow_errors_dev": [_P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P],
     "pdeip_flow_errors": [_P, _P, _P, _P, _P, _I, _I, _P, _P, _P],
+    # cross-checks (csrc/pdeip_crosscheck.hip)
+    "pdeip_disp_crosscheck_dev": [_P, _P, _P, _I, _I, ctypes.c_double, _P, _P, _P, _P],
+    "pdeip_disp_crosscheck": [_P, _P, _I, _I, ctypes.c_double, _P, _P, _P, _P],
+    "pdeip_flow_crosscheck_dev": [_P, _P, _P, _P, _P, _I, _I, ctypes.c_double, ctypes.c_double, _P, _P, _P],
+    "pdeip_flow_crosscheck": [_P, _P, _P, _P, _I, _I, ctypes.c_double, ctypes.c_double, _P, _P, _P],
     # library state
     "pdeip_set_mode": [_I],
     "pdeip_get_mode": [],

@@ -11,26 +11,18 @@
 #include <hip/hip_runtime.h>
 
 #include "pdeip_pointwise.hpp"
+#include "pdeip_sym_warp.hpp"
 
 namespace pdeip {
 
 __constant__ double SYM_PRE[5] = {0.037659, 0.249724, 0.439911, 0.249724, 0.037659};   // prefilter_spa (:71)
 __constant__ double SYM_D1F[5] = {-0.104550, -0.292315, 0.0, 0.292315, 0.104550};      // O_dx (:73) flipped by 'conv'
 
-// out = interp2(X, Y, U, X+Uq, Y): the query rows are the grid rows, so only x is interpolated
+// out = interp2(X, Y, U, X+Uq, Y): the query rows are the grid rows, so only x is interpolated (sym_warp_at, pdeip_sym_warp.hpp)
 __global__ void k_sym_warp_flow(double *out, const float *U, const float *Uq, int nrows, int ncols)
 {
     PDEIP_PIXEL_INDEX();
-    const double xq = (double)(j + 1) + (double)Uq[pos];
-    if (!(xq >= 1.0 && xq <= (double)ncols)) { // also a NaN query
-        out[pos] = __longlong_as_double(0x7ff8000000000000LL);
-        return;
-    }
-    double j0 = floor(xq);
-    if (j0 > (double)(ncols - 1)) j0 = (double)(ncols - 1); // xq == ncols: the last column itself (s = 1)
-    const double s = xq - j0;
-    const int c0 = (int)j0 - 1, c1 = min(c0 + 1, ncols - 1);
-    out[pos] = (double)U[(size_t)c0 * nrows + i] * (1.0 - s) + (double)U[(size_t)c1 * nrows + i] * s;
+    out[pos] = sym_warp_at(U, Uq[pos], i, j, nrows, ncols);
 }
 
 // Udt = (U + Uw)*0.5; Udx = imfilter(imfilter(Uw, prefilter_spa', 'replicate', 'conv'), O_dx, 'replicate', 'conv');

@@ -825,3 +825,54 @@ def flow_errors(U, V, Ut, Vt, mask=None, epe_out=None, ang_out=None, stats_out=N
     capi.call("pdeip_flow_errors_dev", _stream(), *_p(U, V, Ut, Vt), None if mask is None else mask.data_ptr(), nrows, ncols,
               None if epe_out is None else epe_out.data_ptr(), None if ang_out is None else ang_out.data_ptr(), stats_out.data_ptr())
     return epe_out, ang_out, stats_out
+
+
+# ---- cross-checks (csrc/pdeip_crosscheck.hip) ----
+def _out_plane(like, given, wanted, what):
+    if given is None and wanted:
+        given = torch.empty_like(like)
+    if given is not None:
+        _chk_typed(given, torch.float32, like.numel(), what)
+    return given
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def disp_crosscheck(D0, D1, tol=1.0, sparse_out=None, mask_out=None, diff_out=None, stats_out=None, planes=True):
+    """The left-right check of the resident disparity D0 against the other view's D1 (pdeip_disp_crosscheck_dev), both [ncols, nrows].
+    Returns (sparse, mask, diff, stats): D0 where kept and NaN elsewhere, 1 / 0, D0 + the sampled D1 (planes like D0; with
+    planes=False only those handed in are written, the others are None) and a float64 tensor [4] = kept, defined, mean |diff|, largest
+    |diff|.  sparse_out may be D0.  Nothing is read back."""
+    _chk(D0, D1)
+    if D0.dim() != 2 or D1.shape != D0.shape:
+        raise capi.PdeipError(capi.PDEIP_ERR_ARG, "disp_crosscheck: D0 and D1 must be planes [ncols, nrows] of one shape")
+    nrows, ncols, _ = _dims(D0)
+    sparse_out = _out_plane(D0, sparse_out, planes, "disp_crosscheck: sparse_out")
+    mask_out = _out_plane(D0, mask_out, planes, "disp_crosscheck: mask_out")
+    diff_out = _out_plane(D0, diff_out, planes, "disp_crosscheck: diff_out")
+    if stats_out is None:
+        stats_out = torch.empty(4, dtype=torch.float64, device=D0.device)
+    _chk_typed(stats_out, torch.float64, 4, "disp_crosscheck: stats_out")
+    capi.call("pdeip_disp_crosscheck_dev", _stream(), *_p(D0, D1), nrows, ncols, float(tol), _ptr(sparse_out), _ptr(mask_out),
+              _ptr(diff_out), stats_out.data_ptr())
+    return sparse_out, mask_out, diff_out, stats_out
+
+
+def flow_crosscheck(Uf, Vf, Ub, Vb, a=0.01, b=0.5, mask_out=None, err_out=None, stats_out=None, planes=True):
+    """The forward-backward check of the resident flow (Uf, Vf) of frame 0 -> 1 against (Ub, Vb) of frame 1 -> 0
+    (pdeip_flow_crosscheck_dev).  Returns (mask, err, stats): 1 / 0, |f + b(x + f)| (planes like Uf; None with planes=False unless
+    handed in) and a float64 tensor [4] = kept, defined, mean err, largest err.  mask is what flow_errors takes.  Nothing is read back."""
+    _chk(Uf, Vf, Ub, Vb)
+    if Uf.dim() != 2 or any(t.shape != Uf.shape for t in (Vf, Ub, Vb)):
+        raise capi.PdeipError(capi.PDEIP_ERR_ARG, "flow_crosscheck: Uf, Vf, Ub and Vb must be planes [ncols, nrows] of one shape")
+    nrows, ncols, _ = _dims(Uf)
+    mask_out = _out_plane(Uf, mask_out, planes, "flow_crosscheck: mask_out")
+    err_out = _out_plane(Uf, err_out, planes, "flow_crosscheck: err_out")
+    if stats_out is None:
+        stats_out = torch.empty(4, dtype=torch.float64, device=Uf.device)
+    _chk_typed(stats_out, torch.float64, 4, "flow_crosscheck: stats_out")
+    capi.call("pdeip_flow_crosscheck_dev", _stream(), *_p(Uf, Vf, Ub, Vb), nrows, ncols, float(a), float(b), _ptr(mask_out), _ptr(err_out),
+              stats_out.data_ptr())
+    return mask_out, err_out, stats_out

@@ -17,6 +17,7 @@ capi.MODE_RED_BLACK the parallel one).
     regionCompetition           matlab/segmentation/DispSegmentation.m:448-654    region competition of the segmentation drivers
     segments_numbered           matlab/segmentation/DispSegmentation.m:190-198    (C++ only: pdeip_region_competition, pdeip_seg_label)
     flow2color / flow_errors    matlab/optical_flow/flow2color.m                  colour coding; error measures (C++ only: pdeip_flow2color)
+    disp_crosscheck / flow_crosscheck / stereo_maps   this library's own: left-right and forward-backward checks (pdeip_disp_crosscheck)
 
 `Us=`, `Vs=` (param.Us / param.Vs: spatial a-priori fields, double, NaN = no constraint) and `scales=` (param.scales) are taken
 by the late-linearisation flow drivers and the disparity driver as the reference's drivers take them.
@@ -220,8 +221,8 @@ def DispEminND_llin_2D(Il, Ir, fstTerm="rgb", sndTerm="none", mode=capi.MODE_EXA
 SYM_DEFAULTS = dict(alpha=0.035, beta=0.4, omega=1.9, firstLoop=3, secondLoop=4, iter=4, b1=0.25, b2=0.72, scl_factor=0.75, solver=2)
 
 
-def DispEminND_llin_sym_2D(Il, Ir, mode=capi.MODE_EXACT_ORDER, **param):
-    """-> U [nrows, ncols, 2] (left-to-right and right-to-left disparity)."""
+def _disp_sym_planes(Il, Ir, mode, param):
+    """The level loop of DispEminND_llin_sym_2D: the two disparities as resident planes [ncols, nrows]; nothing is downloaded."""
     p = dict(SYM_DEFAULTS, **param)
     # no /255 in this driver (:81-82); its coarsest scale stays unsmoothed (:94-98)
     P0, P1 = pyramid.build_dev(_c3(Il), _c3(Ir), p["scl_factor"], 10, pyramid.gaussian(3, 1.0), smooth_last=False)
@@ -234,8 +235,30 @@ def DispEminND_llin_sym_2D(Il, Ir, mode=capi.MODE_EXACT_ORDER, **param):
         if scl > 0:
             cols, rows = P0[scl - 1].shape[-2:]
             U0, U1 = _up(U0, 1.0 / p["scl_factor"], rows, cols), _up(U1, 1.0 / p["scl_factor"], rows, cols)
+    return U0, U1
+
+
+def DispEminND_llin_sym_2D(Il, Ir, mode=capi.MODE_EXACT_ORDER, **param):
+    """-> U [nrows, ncols, 2] (left-to-right and right-to-left disparity)."""
+    U0, U1 = _disp_sym_planes(Il, Ir, mode, param)
     dev.sync_check()
     return np.stack([dev.to_matlab(U0), dev.to_matlab(U1)], axis=2)
+
+
+def stereo_maps(Il, Ir, tol=1.0, mode=capi.MODE_EXACT_ORDER, **param):
+    """DispEminND_llin_sym_2D followed by the left-right check of its two views against each other (device.disp_crosscheck), all on
+    the device with one download at the end.  Returns a dict: dense [rows, cols, 2], the driver's two disparities; sparse
+    [rows, cols, 2], the same with NaN where a view disagrees with the other by more than tol pixels or looks outside it; mask
+    [rows, cols, 2], 1 where kept; stats, two vectors {kept, defined, mean |r|, largest |r|}.  sparse[:, :, 0] is a map as
+    DispSegmentationSparse, nanmedfilt2 and sparse_pyramid take it."""
+    U0, U1 = _disp_sym_planes(Il, Ir, mode, param)
+    U0, U1 = U0.contiguous(), U1.contiguous()
+    checked = [dev.disp_crosscheck(a, b, tol=tol, sparse_out=torch.empty_like(a), mask_out=torch.empty_like(a), planes=False)
+               for a, b in ((U0, U1), (U1, U0))]
+    dev.sync_check()
+    down = lambda k, src: np.stack([dev.to_matlab(src[0][k]), dev.to_matlab(src[1][k])], axis=2)
+    return dict(dense=np.stack([dev.to_matlab(U0), dev.to_matlab(U1)], axis=2), sparse=down(0, checked), mask=down(1, checked),
+                stats=[c[3].cpu().numpy() for c in checked])
 
 
 def _tv(I_in, level_cls, p, G, smooth_last):
@@ -806,3 +829,45 @@ def flow_errors(U, V, Utrue, Vtrue, mask=None):
     capi.call("pdeip_flow_errors", *[p.ctypes.data for p in planes], None if m is None else m.ctypes.data, rows, cols, epe.ctypes.data,
               ang.ctypes.data, ctypes.addressof(stats))
     return dict(epe=epe, ang=ang, count=int(stats[0]), mean_epe=stats[1], mean_ang=stats[2], max_epe=stats[3])
+
+
+def _same_planes(who, names, arrays):
+    planes = [np.asfortranarray(np.asarray(a, dtype=np.float32)) for a in arrays]
+    if planes[0].ndim != 2 or any(p.shape != planes[0].shape for p in planes):
+        raise ValueError("%s: %s must be [rows, cols] arrays of one shape" % (who, names))
+    return planes
+
+
+def _threshold(who, name, v):
+    v = float(v)
+    if not v >= 0.0:
+        raise ValueError("%s: %s must be >= 0 and not NaN (got %r)" % (who, name, v))
+    return v
+
+
+def disp_crosscheck(D0, D1, tol=1.0):
+    """The left-right check of the disparity D0 against the other view's D1 in one pdeip_disp_crosscheck call (include/pdeip.h): a
+    pixel is kept when D1, sampled linearly at x + D0, cancels D0 to within tol pixels.  Returns a dict: sparse (D0 where kept, NaN
+    elsewhere), mask (1 / 0), diff (D0 + the sampled D1, NaN where the sample is undefined) as single planes; kept, defined, mean, max."""
+    d0, d1 = _same_planes("disp_crosscheck", "D0 and D1", (D0, D1))
+    tol = _threshold("disp_crosscheck", "tol", tol)
+    rows, cols = d0.shape
+    sparse, mask, diff = (np.empty((rows, cols), np.float32, order="F") for _ in range(3))
+    stats = (ctypes.c_double * 4)()
+    capi.call("pdeip_disp_crosscheck", d0.ctypes.data, d1.ctypes.data, rows, cols, tol, sparse.ctypes.data, mask.ctypes.data,
+              diff.ctypes.data, ctypes.addressof(stats))
+    return dict(sparse=sparse, mask=mask, diff=diff, kept=int(stats[0]), defined=int(stats[1]), mean=stats[2], max=stats[3])
+
+
+def flow_crosscheck(Uf, Vf, Ub, Vb, a=0.01, b=0.5):
+    """The forward-backward check of the flow (Uf, Vf) of frame 0 -> 1 against (Ub, Vb) of frame 1 -> 0 in one pdeip_flow_crosscheck
+    call: a pixel is kept when |f + b(x + f)|^2 <= a (|f|^2 + |b|^2) + b (Sundaram, Brox, Keutzer 2010).  Returns a dict: mask (1 / 0)
+    and err (|f + b(x + f)|, NaN where the sample is undefined) as single planes; kept, defined, mean, max."""
+    planes = _same_planes("flow_crosscheck", "Uf, Vf, Ub and Vb", (Uf, Vf, Ub, Vb))
+    a, b = _threshold("flow_crosscheck", "a", a), _threshold("flow_crosscheck", "b", b)
+    rows, cols = planes[0].shape
+    mask, err = np.empty((rows, cols), np.float32, order="F"), np.empty((rows, cols), np.float32, order="F")
+    stats = (ctypes.c_double * 4)()
+    capi.call("pdeip_flow_crosscheck", *[p.ctypes.data for p in planes], rows, cols, a, b, mask.ctypes.data, err.ctypes.data,
+              ctypes.addressof(stats))
+    return dict(mask=mask, err=err, kept=int(stats[0]), defined=int(stats[1]), mean=stats[2], max=stats[3])
