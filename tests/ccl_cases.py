@@ -100,7 +100,13 @@ def names():
 
 
 def get(name):
-    return dict(cases())[name]
+    """A case of this list or of ccl_edge_cases.py (which imports this module, hence the late import)."""
+    own = dict(cases())
+    if name in own:
+        return own[name]
+    import ccl_edge_cases
+
+    return ccl_edge_cases.get(name)
 
 
 def admits_small(A):

@@ -49,7 +49,7 @@ def _run(pdeip, A, conn, cap):
 
     dev = _dev()
     lib = pdeip.capi.load()
-    tA = dev.to_device(np.asfortranarray(A))
+    tA = dev.to_device(np.array(A, order="F"))  # a copy: the cases may be read-only
     buf = torch.full((cap + PAD,), -7, dtype=torch.int32, device="cuda")
     L, num, _ = dev.bwlabel(tA, conn, areas_out=buf[:cap] if cap else None)
     n_bw = lib.pdeip_last_launch_count()
@@ -71,8 +71,9 @@ def _params():
     return out
 
 
-@pytest.mark.parametrize("name,conn,small", _params())
-def test_labels_areas_and_largest_component_equal_the_flood_fill(pdeip, name, conn, small):
+def check_case(pdeip, name, conn, small):
+    """Everything both calls give on one mask in one form against the flood fill, and the form that ran from the launch count;
+    test_gpu_ccl_edges.py runs the masks of ccl_edge_cases.py through it."""
     A = ccl_cases.get(name)
     wL, wnum, wareas, wsel, warea = reference(name, conn)
     with form(small):
@@ -88,6 +89,11 @@ def test_labels_areas_and_largest_component_equal_the_flood_fill(pdeip, name, co
     assert sel.dtype == np.float32 and sel.tobytes() == np.ascontiguousarray(wsel).tobytes()
     for a, b in zip(got, again):  # two calls on the same mask give the same bits
         assert np.array_equal(a, b)
+
+
+@pytest.mark.parametrize("name,conn,small", _params())
+def test_labels_areas_and_largest_component_equal_the_flood_fill(pdeip, name, conn, small):
+    check_case(pdeip, name, conn, small)
 
 
 @pytest.mark.parametrize("small", (False, True))
