@@ -1102,6 +1102,67 @@ int pdeip_flow_crosscheck_dev(void *stream, const float *Uf, const float *Vf, co
 int pdeip_flow_crosscheck(const float *Uf, const float *Vf, const float *Ub, const float *Vb, int nrows, int ncols, double a, double b,
                           float *mask_out, float *err_out, double *stats_out);
 
+/* ---- hole filling: total-variation inpainting of a sparse map (csrc/pdeip_inpaint.hip) ---------------------------------------------
+ *
+ * This library's own definitions (the reference has no such driver; its solvers carry the mechanism: a pixel whose TRACE is NaN has
+ * "no data", pdeSolvers.c:101-114).  Planes are column-major float32 [nrows x ncols (x frames)].  A pixel of D is a hole if it is
+ * NaN, per frame; every other value (Inf included) is known.  Single arithmetic without FMA unless stated otherwise.
+ *
+ * pdeip_nan_resize_dev: with resize = pdeip_pyr_resize_dev(cubic = 0) kept in double,
+ *   num = resize(known ? D : 0), den = resize(known ? 1 : 0), out = den >= cover ? (float)(num / den) : NaN.
+ * One thread per output pixel walks the tap lists once and accumulates both sums in that order.  cover in (0, 1]; the size limits
+ * of pdeip_pyr_resize_dev apply.
+ *
+ * pdeip_inpaint_meanfill_dev: per frame the known values are summed in double, each column top to bottom starting from 0, the column
+ * sums then left to right starting from 0; mean = (float)(sum / count), 0 for a frame without a known pixel.  out = D where known
+ * (its bits), the mean on holes.  out may be D.
+ *
+ * pdeip_tv4_inpaint_assemble_dev: the weights are TVdenoise4.m's DiffWeights (pdeip_tv4_assemble_dev), their maximum over the frames
+ * taken over the `nframes` frames of X followed by the guide_channels planes of (float)guide_scale * guide (guide NULL with 0
+ * channels).  On a known pixel psi = 1/sqrt((X-D)^2 + eps), TRACE = psi + alpha*(wW+wN+wE+wS), B = psi*D; on a hole TRACE = NaN,
+ * B = 0, and D's NaN enters no arithmetic.  The weight planes hold alpha*w, repeated per frame.  With no hole and no guide the
+ * outputs are pdeip_tv4_assemble_dev's, bit for bit.
+ *
+ * pdeip_inpaint_merge_dev: out = D where known (its own bits, -0.0 included), X elsewhere; filled_out (NULL allowed) = 1 on holes,
+ * 0 elsewhere.  out may be X or D.
+ *
+ * Each of the four is one launch on `stream`, whatever the data (pdeip_last_launch_count()).
+ *
+ * pdeip_tv_inpaint4 (host pointers) / pdeip_tv_inpaint4_dev (resident planes): D [nrows x ncols x frames], guide
+ * [nrows x ncols x guide_channels] or NULL with 0 channels, out like D, filled_out like D or NULL.
+ *   pyramid   level k+1 has ceil(size*scl_factor) rows and columns, D through pdeip_nan_resize_dev(cover), the guide through
+ *             pdeip_pyr_resize_dev, no smoothing; it continues while the smaller side of the next level is >= max(min_size, 3) and
+ *             the frame still shrinks
+ *   start     X = pdeip_inpaint_meanfill_dev of the coarsest D
+ *   level     outer_iter + 1 times [pdeip_tv4_inpaint_assemble_dev; pdeip_pde_sor4_dev | pdeip_pde_alr4_dev(inner_iter, omega)] in
+ *             the library's current mode (pdeip_set_mode), coarse to fine; X goes up through pdeip_pyr_resize_dev
+ *   end       keep: pdeip_inpaint_merge_dev; otherwise out = X (filled_out is written either way)
+ * A flow is filled by handing U, V as two frames: the weights are then joint, as in TVdenoise4.
+ * A member of the parameter struct that is <= 0 or NaN keeps its default (alpha 5, omega 1.75, outer_iter 10, inner_iter 5,
+ * solver 2, scl_factor 0.75, min_size 16, cover 0.25, guide_scale 20); keep: 0 = no merge, > 0 = merge, < 0 = the default (merge).
+ * NULL: all defaults.
+ * _dev: launches on `stream`, nothing read back, no control flow on the data (the launch count depends on shape and parameters
+ * alone); graph-capturable once an eager call has created the workspace.
+ * Refused with PDEIP_ERR_ARG before any HIP call: NULL D or out, a frame below 3x3, frames < 1, more than 2^31-1 elements,
+ * scl_factor not below 1, cover above 1, an unknown solver, guide_channels < 0, a guide pointer that disagrees with its channel
+ * count; PDEIP_ERR_UNSUPPORTED: more than 65535 columns, a scl_factor that needs more taps than pdeip_pyr_resize_dev has. */
+typedef struct pdeip_inpaint_params {
+    double alpha, omega, scl_factor, cover, guide_scale;
+    int outer_iter, inner_iter, solver, min_size, keep;
+} pdeip_inpaint_params;
+int pdeip_nan_resize_dev(void *stream, const float *in, int nrows, int ncols, int nframes, int nrows_out, int ncols_out, double cover,
+                         float *out);
+int pdeip_inpaint_meanfill_dev(void *stream, const float *D, int nrows, int ncols, int nframes, float *out);
+int pdeip_tv4_inpaint_assemble_dev(void *stream, const float *X, const float *D, const float *guide, int guide_channels,
+                                   double guide_scale, int nrows, int ncols, int nframes, float alpha, float *TRACE, float *B,
+                                   float *wW, float *wN, float *wE, float *wS);
+int pdeip_inpaint_merge_dev(void *stream, const float *X, const float *D, int nrows, int ncols, int nframes, float *out,
+                            float *filled_out);
+int pdeip_tv_inpaint4_dev(void *stream, const float *D, int nrows, int ncols, int frames, const float *guide, int guide_channels,
+                          const pdeip_inpaint_params *prm, float *out, float *filled_out);
+int pdeip_tv_inpaint4(const float *D, int nrows, int ncols, int frames, const float *guide, int guide_channels,
+                      const pdeip_inpaint_params *prm, float *out, float *filled_out);
+
 #ifdef __cplusplus
 }
 #endif

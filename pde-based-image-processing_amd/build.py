@@ -36,6 +36,7 @@ UNITS = {
     "pdeip_ccl.hip": ["pdeip_ccl.hpp", "pdeip_ccl_plan.hpp"],
     "pdeip_flowviz.hip": ["pdeip_flowviz.hpp", "pdeip_reduce.hpp"],
     "pdeip_crosscheck.hip": ["pdeip_crosscheck.hpp", "pdeip_sym_warp.hpp", "pdeip_reduce.hpp"],
+    "pdeip_inpaint.hip": ["pdeip_inpaint.hpp", "pdeip_pyr.hpp", "pdeip_pointwise.hpp"],
 }
 # -ffp-contract=off is part of the parity contract (the reference is FMA-free C).
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]

@@ -181,6 +181,13 @@ SIGNATURES = {
     "pdeip_disp_crosscheck": [_P, _P, _I, _I, ctypes.c_double, _P, _P, _P, _P],
     "pdeip_flow_crosscheck_dev": [_P, _P, _P, _P, _P, _I, _I, ctypes.c_double, ctypes.c_double, _P, _P, _P],
     "pdeip_flow_crosscheck": [_P, _P, _P, _P, _I, _I, ctypes.c_double, ctypes.c_double, _P, _P, _P],
+    # hole filling (csrc/pdeip_inpaint.hip)
+    "pdeip_nan_resize_dev": [_P, _P, _I, _I, _I, _I, _I, ctypes.c_double, _P],
+    "pdeip_inpaint_meanfill_dev": [_P, _P, _I, _I, _I, _P],
+    "pdeip_tv4_inpaint_assemble_dev": [_P, _P, _P, _P, _I, ctypes.c_double, _I, _I, _I, _F] + [_P] * 6,
+    "pdeip_inpaint_merge_dev": [_P, _P, _P, _I, _I, _I, _P, _P],
+    "pdeip_tv_inpaint4_dev": [_P, _P, _I, _I, _I, _P, _I, _P, _P, _P],
+    "pdeip_tv_inpaint4": [_P, _I, _I, _I, _P, _I, _P, _P, _P],
     # library state
     "pdeip_set_mode": [_I],
     "pdeip_get_mode": [],

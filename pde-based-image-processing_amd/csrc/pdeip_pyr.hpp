@@ -16,6 +16,18 @@ struct PyrAxis {
     int T, cubic;
 };
 
+// The tap list of one axis (pyramid._resize_taps): host side, shared by every call that launches a kernel walking it.
+inline PyrAxis pyr_axis_of(int n_in, int n_out, int cubic)
+{
+    PyrAxis A;
+    A.scale = (double)n_out / (double)n_in;
+    A.stretch = A.scale >= 1.0 ? 1.0 : 1.0 / A.scale;
+    A.width = (cubic ? 2.0 : 1.0) * A.stretch;
+    A.T = (int)ceil(2.0 * A.width) + 2;
+    A.cubic = cubic;
+    return A;
+}
+
 __device__ __forceinline__ double pyr_weight(const PyrAxis &A, double x, int idx)
 {
     const double a = fabs(((double)idx - x) / A.stretch);
@@ -27,7 +39,7 @@ __device__ __forceinline__ double pyr_weight(const PyrAxis &A, double x, int idx
 }
 
 // pyramid.resize: rows first, then columns
-__global__ void k_pyr_resize(float *out, const float *in, PyrAxis R, PyrAxis C, int nrows_in, int ncols_in, int nrows, int ncols)
+static __global__ void k_pyr_resize(float *out, const float *in, PyrAxis R, PyrAxis C, int nrows_in, int ncols_in, int nrows, int ncols)
 {
     PDEIP_PIXEL_INDEX();
     const float *src = in + (size_t)blockIdx.z * nrows_in * ncols_in;
@@ -62,7 +74,7 @@ struct PyrMask {
 };
 
 // pyramid.smooth: imfilter(I, G, 'replicate'), double accumulation in mask order
-__global__ void k_pyr_smooth(float *out, const float *in, PyrMask M, int nrows, int ncols)
+static __global__ void k_pyr_smooth(float *out, const float *in, PyrMask M, int nrows, int ncols)
 {
     PDEIP_PIXEL_INDEX();
     const size_t fo = (size_t)blockIdx.z * nrows * ncols;

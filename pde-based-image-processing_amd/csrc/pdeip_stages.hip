@@ -473,11 +473,7 @@ extern "C" int pdeip_tv_assemble_dev(void *stream, const float *Iout, const floa
 // ---- image pyramid (pdeip_pyr.hpp) ---------------------------------------------------------------------
 static int pyr_axis(const char *who, int n_in, int n_out, int cubic, PyrAxis *A)
 {
-    A->scale = (double)n_out / (double)n_in;
-    A->stretch = A->scale >= 1.0 ? 1.0 : 1.0 / A->scale;
-    A->width = (cubic ? 2.0 : 1.0) * A->stretch;
-    A->T = (int)ceil(2.0 * A->width) + 2;
-    A->cubic = cubic;
+    *A = pyr_axis_of(n_in, n_out, cubic);
     if (A->T > PYR_TMAX) return set_err(PDEIP_ERR_UNSUPPORTED, "%s: shrinking %d -> %d needs %d taps (at most %d)", who, n_in, n_out, A->T, PYR_TMAX);
     return PDEIP_OK;
 }

@@ -876,3 +876,98 @@ def flow_crosscheck(Uf, Vf, Ub, Vb, a=0.01, b=0.5, mask_out=None, err_out=None, 
     capi.call("pdeip_flow_crosscheck_dev", _stream(), *_p(Uf, Vf, Ub, Vb), nrows, ncols, float(a), float(b), _ptr(mask_out), _ptr(err_out),
               stats_out.data_ptr())
     return mask_out, err_out, stats_out
+
+
+# ---- hole filling: TV inpainting of a sparse map (csrc/pdeip_inpaint.hip) ----
+class InpaintParams(ctypes.Structure):
+    """pdeip_inpaint_params: a member <= 0 keeps the driver's default; keep: 0 no merge, 1 merge."""
+    _fields_ = [(k, ctypes.c_double) for k in ("alpha", "omega", "scl_factor", "cover", "guide_scale")] + \
+               [(k, ctypes.c_int) for k in ("outer_iter", "inner_iter", "solver", "min_size", "keep")]
+
+    @classmethod
+    def make(cls, **param):
+        s = cls(keep=-1)
+        for k, v in param.items():
+            if k not in dict(cls._fields_):
+                raise capi.PdeipError(capi.PDEIP_ERR_ARG, "tv_inpaint4: unknown parameter '%s'" % k)
+            setattr(s, k, type(getattr(s, k))(v))
+        return s
+
+
+def _guide(like, guide, who):
+    """(pointer, channels) of an optional guide [(C,) ncols, nrows] on the frame of `like`."""
+    if guide is None:
+        return None, 0
+    _chk(guide)
+    if guide.shape[-2:] != like.shape[-2:]:
+        raise capi.PdeipError(capi.PDEIP_ERR_ARG, "%s: the guide is %s but the map is %s" % (who, tuple(guide.shape), tuple(like.shape)))
+    return guide.data_ptr(), _dims(guide)[2]
+
+
+def nan_resize(D, nrows_out, ncols_out, cover=0.25):
+    """The NaN-aware pyramid.resize (bilinear): [(F,) ncols, nrows] -> [(F,) ncols_out, nrows_out]; a pixel whose known taps weigh
+    less than `cover` is NaN."""
+    _chk(D)
+    nrows, ncols, F = _dims(D)
+    out = torch.empty(D.shape[:-2] + (int(ncols_out), int(nrows_out)), dtype=D.dtype, device=D.device)
+    capi.call("pdeip_nan_resize_dev", _stream(), D.data_ptr(), nrows, ncols, F, int(nrows_out), int(ncols_out), float(cover), out.data_ptr())
+    return out
+
+
+def inpaint_meanfill(D, out=None):
+    """Holes (NaN) take the mean of their frame's known values, known pixels keep their bits."""
+    _chk(D)
+    out = torch.empty_like(D) if out is None else out
+    _chk_typed(out, torch.float32, D.numel(), "inpaint_meanfill: out")
+    nrows, ncols, F = _dims(D)
+    capi.call("pdeip_inpaint_meanfill_dev", _stream(), D.data_ptr(), nrows, ncols, F, out.data_ptr())
+    return out
+
+
+def tv4_inpaint_assemble(X, D, alpha, TRACE, B, w4, guide=None, guide_scale=20.0):
+    """tv4_assemble for a sparse D: NaN TRACE and zero B on holes, the weights' maximum also over guide_scale * guide;
+    w4 = [aW, aN, aE, aS]."""
+    _chk(X, D, TRACE, B, *w4)
+    if any(t.shape != X.shape for t in (D, TRACE, B, *w4)):
+        raise capi.PdeipError(capi.PDEIP_ERR_ARG, "tv4_inpaint_assemble: X, D, TRACE, B and the weights must have one shape")
+    gp, gc = _guide(X, guide, "tv4_inpaint_assemble")
+    nrows, ncols, F = _dims(X)
+    capi.call("pdeip_tv4_inpaint_assemble_dev", _stream(), *_p(X, D), gp, gc, float(guide_scale), nrows, ncols, F, float(alpha),
+              *_p(TRACE, B, *w4))
+
+
+def inpaint_merge(X, D, out=None, filled_out=None):
+    """out = D where D is a number (its own bits), X elsewhere; filled_out (optional) = 1 on holes.  Returns out."""
+    _chk(X, D)
+    if D.shape != X.shape:
+        raise capi.PdeipError(capi.PDEIP_ERR_ARG, "inpaint_merge: X and D must have one shape")
+    out = torch.empty_like(X) if out is None else out
+    _chk_typed(out, torch.float32, X.numel(), "inpaint_merge: out")
+    if filled_out is not None:
+        _chk_typed(filled_out, torch.float32, X.numel(), "inpaint_merge: filled_out")
+    nrows, ncols, F = _dims(X)
+    capi.call("pdeip_inpaint_merge_dev", _stream(), *_p(X, D), nrows, ncols, F, out.data_ptr(), _ptr(filled_out))
+    return out
+
+
+def tv_inpaint4(D, guide=None, out=None, filled_out=None, mode=None, **param):
+    """The whole resident run (pdeip_tv_inpaint4_dev): D [(F,) ncols, nrows] with NaN holes, guide [(C,) ncols, nrows] or None.
+    Returns out (a plane like D).  mode: the ordering of the solver calls (None: the library's current mode).  Nothing is read back."""
+    _chk(D)
+    gp, gc = _guide(D, guide, "tv_inpaint4")
+    out = torch.empty_like(D) if out is None else out
+    _chk_typed(out, torch.float32, D.numel(), "tv_inpaint4: out")
+    if filled_out is not None:
+        _chk_typed(filled_out, torch.float32, D.numel(), "tv_inpaint4: filled_out")
+    nrows, ncols, F = _dims(D)
+    prm = InpaintParams.make(**param)
+    old = capi.get_mode()
+    if mode is not None:
+        capi.set_mode(mode)
+    try:
+        capi.call("pdeip_tv_inpaint4_dev", _stream(), D.data_ptr(), nrows, ncols, F, gp, gc, ctypes.addressof(prm), out.data_ptr(),
+                  _ptr(filled_out))
+    finally:
+        if mode is not None:
+            capi.set_mode(old)
+    return out

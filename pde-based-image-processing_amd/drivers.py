@@ -18,6 +18,7 @@ capi.MODE_RED_BLACK the parallel one).
     segments_numbered           matlab/segmentation/DispSegmentation.m:190-198    (C++ only: pdeip_region_competition, pdeip_seg_label)
     flow2color / flow_errors    matlab/optical_flow/flow2color.m                  colour coding; error measures (C++ only: pdeip_flow2color)
     disp_crosscheck / flow_crosscheck / stereo_maps   this library's own: left-right and forward-backward checks (pdeip_disp_crosscheck)
+    TVinpaint4                  this library's own: the holes of a sparse map filled by TV inpainting (pdeip_tv_inpaint4)
 
 `Us=`, `Vs=` (param.Us / param.Vs: spatial a-priori fields, double, NaN = no constraint) and `scales=` (param.scales) are taken
 by the late-linearisation flow drivers and the disparity driver as the reference's drivers take them.
@@ -245,20 +246,27 @@ def DispEminND_llin_sym_2D(Il, Ir, mode=capi.MODE_EXACT_ORDER, **param):
     return np.stack([dev.to_matlab(U0), dev.to_matlab(U1)], axis=2)
 
 
-def stereo_maps(Il, Ir, tol=1.0, mode=capi.MODE_EXACT_ORDER, **param):
+def stereo_maps(Il, Ir, tol=1.0, mode=capi.MODE_EXACT_ORDER, fill=False, fill_param=None, **param):
     """DispEminND_llin_sym_2D followed by the left-right check of its two views against each other (device.disp_crosscheck), all on
     the device with one download at the end.  Returns a dict: dense [rows, cols, 2], the driver's two disparities; sparse
     [rows, cols, 2], the same with NaN where a view disagrees with the other by more than tol pixels or looks outside it; mask
     [rows, cols, 2], 1 where kept; stats, two vectors {kept, defined, mean |r|, largest |r|}.  sparse[:, :, 0] is a map as
-    DispSegmentationSparse, nanmedfilt2 and sparse_pyramid take it."""
+    DispSegmentationSparse, nanmedfilt2 and sparse_pyramid take it.
+    fill=True: each view's sparse map is inpainted on the device (TVinpaint4 with fill_param, that view's image as the guide) and
+    comes back under the further key filled [rows, cols, 2]."""
+    fp = _inpaint_param("stereo_maps", fill_param or {}) if fill else None
     U0, U1 = _disp_sym_planes(Il, Ir, mode, param)
     U0, U1 = U0.contiguous(), U1.contiguous()
     checked = [dev.disp_crosscheck(a, b, tol=tol, sparse_out=torch.empty_like(a), mask_out=torch.empty_like(a), planes=False)
                for a, b in ((U0, U1), (U1, U0))]
+    filled = [_inpaint_planes(c[0], _c3(I), mode, fp)[0] for c, I in zip(checked, (Il, Ir))] if fill else None
     dev.sync_check()
     down = lambda k, src: np.stack([dev.to_matlab(src[0][k]), dev.to_matlab(src[1][k])], axis=2)
-    return dict(dense=np.stack([dev.to_matlab(U0), dev.to_matlab(U1)], axis=2), sparse=down(0, checked), mask=down(1, checked),
+    maps = dict(dense=np.stack([dev.to_matlab(U0), dev.to_matlab(U1)], axis=2), sparse=down(0, checked), mask=down(1, checked),
                 stats=[c[3].cpu().numpy() for c in checked])
+    if fill:
+        maps["filled"] = np.stack([dev.to_matlab(filled[0]), dev.to_matlab(filled[1])], axis=2)
+    return maps
 
 
 def _tv(I_in, level_cls, p, G, smooth_last):
@@ -871,3 +879,99 @@ def flow_crosscheck(Uf, Vf, Ub, Vb, a=0.01, b=0.5):
     capi.call("pdeip_flow_crosscheck", *[p.ctypes.data for p in planes], rows, cols, a, b, mask.ctypes.data, err.ctypes.data,
               ctypes.addressof(stats))
     return dict(mask=mask, err=err, kept=int(stats[0]), defined=int(stats[1]), mean=stats[2], max=stats[3])
+
+
+# ---- hole filling: a sparse map (NaN = no estimate) made dense by TV inpainting (include/pdeip.h; this library's own driver) ----
+INPAINT_DEFAULTS = dict(alpha=5.0, omega=1.75, outer_iter=10, inner_iter=5, solver=2, scl_factor=0.75, min_size=16, cover=0.25,
+                        guide_scale=20.0, keep=1)
+
+
+def _inpaint_param(who, param):
+    """The defaults filled in as pdeip_tv_inpaint4 fills them (a value <= 0 or NaN keeps its default; keep: < 0), and its refusals."""
+    unknown = set(param) - set(INPAINT_DEFAULTS)
+    if unknown:
+        raise ValueError("%s: unknown parameter %s" % (who, sorted(unknown)))
+    p = dict(INPAINT_DEFAULTS)
+    for k, v in param.items():
+        if k == "keep":
+            p[k] = 1 if int(v) < 0 else int(int(v) != 0)
+        elif v > 0:
+            p[k] = type(INPAINT_DEFAULTS[k])(v)
+    if p["solver"] not in (1, 2):
+        raise ValueError("%s: unknown solver %d (1 point SOR, 2 line relaxation)" % (who, p["solver"]))
+    if not p["scl_factor"] < 1.0:
+        raise ValueError("%s: scl_factor must be below 1 (got %r)" % (who, p["scl_factor"]))
+    if not p["cover"] <= 1.0:
+        raise ValueError("%s: cover must not be above 1 (got %r)" % (who, p["cover"]))
+    return p
+
+
+def _inpaint_planes(D, guide, mode, p, want_filled=False):
+    """The level loop of pdeip_tv_inpaint4_dev composed from the stage calls, on resident planes: D [(F,) ncols, nrows] with NaN
+    holes, guide [(C,) ncols, nrows] or None.  Returns (out, filled or None); nothing is downloaded."""
+    Ds, Gs = [D], [guide]
+    floor = max(int(p["min_size"]), 3)
+    while True:
+        c, r = Ds[-1].shape[-2:]
+        nr, nc = int(math.ceil(r * p["scl_factor"])), int(math.ceil(c * p["scl_factor"]))
+        if min(nr, nc) < floor or (nr == r and nc == c):
+            break
+        Ds.append(dev.nan_resize(Ds[-1], nr, nc, p["cover"]))
+        Gs.append(None if guide is None else dev.pyr_resize(Gs[-1], nr, nc))
+    level = fl.Inpaint4Level(p, mode=mode)
+    X = dev.inpaint_meanfill(Ds[-1])
+    for scl in range(len(Ds) - 1, -1, -1):
+        X = level.run(Ds[scl], X, Gs[scl])
+        if scl > 0:
+            c, r = Ds[scl - 1].shape[-2:]
+            X = dev.pyr_resize(X, r, c)
+    filled = torch.empty_like(D) if want_filled else None
+    if p["keep"]:
+        return dev.inpaint_merge(X, D, filled_out=filled), filled
+    if want_filled:
+        dev.inpaint_merge(X, D, filled_out=filled)
+    return X, filled
+
+
+def _inpaint_inputs(who, D, guide):
+    d = np.asarray(D, dtype=np.float32)
+    if d.ndim not in (2, 3):
+        raise ValueError("%s: D must be [rows, cols] or [rows, cols, frames]" % who)
+    g = None if guide is None else np.asarray(guide, dtype=np.float32)
+    if g is not None and (g.ndim not in (2, 3) or g.shape[:2] != d.shape[:2]):
+        raise ValueError("%s: the guide must be [rows, cols(, channels)] on D's frame" % who)
+    return d, g
+
+
+def TVinpaint4(D, guide=None, mode=capi.MODE_EXACT_ORDER, return_filled=False, **param):
+    """Fill the holes (NaN) of the sparse map D [rows, cols(, frames)] by total-variation inpainting: PDEsolver4 with NaN TRACE on
+    the holes and TVdenoise4's lagged-diffusivity weights, coarse to fine over a NaN-aware pyramid.  guide [rows, cols(, channels)]:
+    an image whose edges (times guide_scale) join the weights, so that a filled region ends where the image says it does.  A flow is
+    filled by passing cat(3, U, V).  param: alpha 5, omega 1.75, outer_iter 10, inner_iter 5, solver 2, scl_factor 0.75, min_size 16,
+    cover 0.25, guide_scale 20, keep 1 (known pixels come back with their own bits).  Returns the dense map, with return_filled also
+    the plane that is 1 on the former holes."""
+    p = _inpaint_param("TVinpaint4", param)
+    d, g = _inpaint_inputs("TVinpaint4", D, guide)
+    out, filled = _inpaint_planes(dev.to_device(d), None if g is None else _c3(g), mode, p, want_filled=return_filled)
+    dev.sync_check()
+    return (dev.to_matlab(out), dev.to_matlab(filled)) if return_filled else dev.to_matlab(out)
+
+
+def capi_TVinpaint4(D, guide=None, mode=capi.MODE_EXACT_ORDER, return_filled=False, **param):
+    """pdeip_tv_inpaint4 on MATLAB-shaped numpy arrays: the C++ twin of TVinpaint4 above, same bits."""
+    d, g = _inpaint_inputs("capi_TVinpaint4", D, guide)
+    d3 = _f_single(d)
+    rows, cols, F = d3.shape
+    g3 = None if g is None else _f_single(g)
+    out = np.zeros((rows, cols, F), np.float32, order="F")
+    filled = np.zeros((rows, cols, F), np.float32, order="F") if return_filled else None
+    prm = dev.InpaintParams.make(**param)
+    old = capi.get_mode()
+    capi.set_mode(mode)
+    try:
+        capi.call("pdeip_tv_inpaint4", d3.ctypes.data, rows, cols, F, None if g3 is None else g3.ctypes.data, 0 if g3 is None else g3.shape[2],
+                  ctypes.addressof(prm), out.ctypes.data, None if filled is None else filled.ctypes.data)
+    finally:
+        capi.set_mode(old)
+    shape = (lambda a: a if d.ndim == 3 else a[:, :, 0])
+    return (shape(out), shape(filled)) if return_filled else shape(out)

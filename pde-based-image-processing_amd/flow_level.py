@@ -269,3 +269,24 @@ class FlowHsLevel:
             fn = dev.oflow_sor_elin4 if int(p["solver"]) == 1 else dev.oflow_alr_elin4
             fn(U, V, *coef, W, W, W, W, int(p["iter"]), float(p["omega"]), self.mode)
         return U, V
+
+
+class Inpaint4Level:
+    """One scale of the TV inpainting of a sparse map (this library's own driver, include/pdeip.h): outer_iter + 1 times
+    [tv4_inpaint_assemble, PDEsolver4], Tv4Level's loop with NaN TRACE on the holes of D and an optional guide in the weights.
+    param: alpha, omega, outer_iter, inner_iter, solver, guide_scale."""
+
+    def __init__(self, param, mode=capi.MODE_EXACT_ORDER):
+        self.p, self.mode = dict(param), mode
+
+    def run(self, D, X, guide=None):
+        """D: the scale's sparse map, X: the estimate entering it (no NaN), guide: [(C,) ncols, nrows] or None."""
+        p = self.p
+        X = X.clone()
+        TRACE, B = torch.empty_like(X), torch.empty_like(X)
+        w4 = [torch.empty_like(X) for _ in range(4)]  # aW, aN, aE, aS
+        solve = dev.pde_sor4 if int(p["solver"]) == 1 else dev.pde_alr4
+        for _ in range(int(p["outer_iter"]) + 1):
+            dev.tv4_inpaint_assemble(X, D, p["alpha"], TRACE, B, w4, guide, p.get("guide_scale", 20.0))
+            solve(X, TRACE, B, w4[0], w4[1], w4[2], w4[3], int(p["inner_iter"]), float(p["omega"]), self.mode)
+        return X
