@@ -1163,6 +1163,82 @@ int pdeip_tv_inpaint4_dev(void *stream, const float *D, int nrows, int ncols, in
 int pdeip_tv_inpaint4(const float *D, int nrows, int ncols, int frames, const float *guide, int guide_channels,
                       const pdeip_inpaint_params *prm, float *out, float *filled_out);
 
+/* ---- frame interpolation: the picture between two frames, from a computed flow (csrc/pdeip_interp.hip) ------------------------------
+ *
+ * This library's own definitions (the reference has no such function); the algorithm is the baseline of Baker et al., "A Database and
+ * Evaluation Methodology for Optical Flow", IJCV 2011, section 3.3.  Planes are column-major float32 [nrows x ncols (x channels)],
+ * coordinates 1-based (x = j+1, y = i+1 for the 0-based pixel (i, j)) as in pdeip_flow_crosscheck.  All arithmetic is float64 on the
+ * promoted inputs, every product and sum rounded, no FMA, one rounding to float32 on the way out.  0 < t < 1; tq = 1 - t is formed
+ * once on the host.  B(A) at (xq, yq) is the bilinear sample of pdeip_flow_crosscheck, one device function for all: in range iff
+ * 1 <= xq <= ncols and 1 <= yq <= nrows, the same clamps, the same order of operations.
+ *
+ * pdeip_flow_splat_dev: the flow (Uf, Vf) of frame 0 -> 1 carried forward to time t.
+ *   source   a pixel p = (i, j) with Uf[p], Vf[p] finite; any other pixel splats nothing
+ *   cost     with I0, I1 [nrows x ncols x channels] given: c = (float) sum over ch ascending of |I0[p,ch] - B(I1[:,:,ch])| at
+ *            (x + Uf, y + Vf), the sum started at 0; out of range, or a NaN sum: c = +Inf.  With I0 == I1 == NULL: c = 0.
+ *            c >= +0, so its bit pattern orders as an unsigned integer.
+ *   landing  xq = x + t Uf, yq = y + t Vf
+ *   targets  columns floor(xq) and, only if xq is not an integer, floor(xq)+1; rows alike: one, two or four pixels, those outside
+ *            the frame dropped
+ *   winner   per target the smallest 64-bit key (bits(c) << 32) | p, p the 0-based linear index j nrows + i: the lowest cost, ties
+ *            to the lowest index.  Keys meet in an integer atomicMin on a plane cleared to all ones, so the order of arrival does
+ *            not matter and a call is reproducible to the bit.
+ *   resolve  a target no key reached is a hole: Ut = Vt = NaN, cost = NaN.  Otherwise Ut, Vt are the winner's Uf, Vf with their own
+ *            bits (-0.0 stays -0.0) and cost_out (NULL allowed) its c.
+ * 3 launches (clear, splat, resolve), whatever the data.  Workspace: the key plane, 8 bytes per pixel.
+ * Refused with PDEIP_ERR_ARG before any HIP call: NULL Uf, Vf, Ut_out or Vt_out; only one of I0, I1; channels < 1 with images; t not
+ * in (0, 1) or NaN; a plane below 3x3; more than 2^31-1 pixels; an output pointer equal to an input pointer.
+ * PDEIP_ERR_UNSUPPORTED: more than 65535 columns.
+ *
+ * pdeip_interp_blend_dev: the picture at time t along a dense flow (Ut, Vt) given at time t.  Per pixel, (u, v) = (Ut, Vt) there:
+ *   q0 = (x - t u, y - t v) in frame 0, q1 = (x + tq u, y + tq v) in frame 1
+ *   r0, r1   u and v finite and the point in range
+ *   a0 = B(I0) at q0, a1 = B(I1) at q1, per channel
+ *   p0 = (M0 == NULL) || M0[nearest(q0)] != 0, p1 alike with M1 at q1; nearest: column min(floor(xq + 0.5), ncols), row alike.
+ *        M0, M1 (both or neither) are the masks pdeip_flow_crosscheck writes, 1 = consistent: M0 for the forward flow in frame 0,
+ *        M1 for the backward flow in frame 1.
+ *   case                 It_out                    source_out
+ *   neither in range     NaN on every channel      0
+ *   only r0              a0                        1
+ *   only r1              a1                        2
+ *   both, p0 == p1       (float)(tq a0 + t a1)     3
+ *   both, p0 && !p1      a1                        2
+ *   both, !p0 && p1      a0                        1
+ * The last two rows are Baker's occlusion reasoning: a sample that fails its own view's check shows what only that view sees (a
+ * background pixel about to be covered exists in frame 0 alone, one just revealed in frame 1 alone), so it is the one taken; the
+ * sample that passes its check at that place is the occluder.
+ * 1 launch; source_out may be NULL.  Refused as above, and: NULL I0, I1, Ut, Vt or It_out; channels < 1; only one of M0, M1.
+ *
+ * pdeip_flow_interpolate (host pointers) / pdeip_flow_interpolate_dev (resident planes), in this order:
+ *   1  with Ub, Vb (both or neither), the flow of frame 1 -> 0: M0 = mask of pdeip_flow_crosscheck_dev(Uf, Vf | Ub, Vb; a, b) and
+ *      M1 = mask of pdeip_flow_crosscheck_dev(Ub, Vb | Uf, Vf; a, b), no statistics
+ *   2  pdeip_flow_splat_dev, with the costs of I0, I1 unless use_costs == 0
+ *   3  pdeip_tv_inpaint4_dev on (Ut, Vt) as two frames, no guide, parameters `fill` (NULL: its defaults), in the library's current mode
+ *   4  pdeip_interp_blend_dev along the filled flow, with M0, M1 if step 1 ran
+ * Ut_out, Vt_out (each may be NULL) receive the filled flow at t; source_out may be NULL.  A parameter struct is taken as it stands
+ * (a = 0 is an absolute threshold); NULL: a = 0.01, b = 0.5, use_costs = 1, fill = NULL.
+ * A field without any finite source is an all-hole plane to step 3, which fills it with zeros: the result is the zero-flow blend.
+ * _dev: launches on `stream`, nothing read back, graph-capturable once an eager call has created the workspaces.  The launch count
+ * depends on shape and parameters alone and is the sum of its parts: [2] + 3 + pdeip_tv_inpaint4_dev's + 1, plus one copy per
+ * Ut_out / Vt_out given (pdeip_last_launch_count()).
+ * Refused before any HIP call: what the parts refuse (a, b NaN or negative; the hole filling's parameters), NULL I0, I1, Uf, Vf or
+ * It_out, only one of Ub, Vb, an output pointer equal to an input pointer. */
+typedef struct pdeip_interp_params {
+    double a, b;
+    int use_costs;
+    const pdeip_inpaint_params *fill;
+} pdeip_interp_params;
+int pdeip_flow_splat_dev(void *stream, const float *Uf, const float *Vf, const float *I0, const float *I1, int channels, int nrows,
+                         int ncols, double t, float *Ut_out, float *Vt_out, float *cost_out);
+int pdeip_interp_blend_dev(void *stream, const float *I0, const float *I1, int channels, const float *Ut, const float *Vt,
+                           const float *M0, const float *M1, int nrows, int ncols, double t, float *It_out, float *source_out);
+int pdeip_flow_interpolate_dev(void *stream, const float *I0, const float *I1, int channels, const float *Uf, const float *Vf,
+                               const float *Ub, const float *Vb, int nrows, int ncols, double t, const pdeip_interp_params *prm,
+                               float *It_out, float *Ut_out, float *Vt_out, float *source_out);
+int pdeip_flow_interpolate(const float *I0, const float *I1, int channels, const float *Uf, const float *Vf, const float *Ub,
+                           const float *Vb, int nrows, int ncols, double t, const pdeip_interp_params *prm, float *It_out,
+                           float *Ut_out, float *Vt_out, float *source_out);
+
 #ifdef __cplusplus
 }
 #endif

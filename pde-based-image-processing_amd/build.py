@@ -35,8 +35,9 @@ UNITS = {
     "pdeip_sparse.hip": ["pdeip_sparse.hpp", "pdeip_cswap.hpp", "pdeip_models.hpp", "pdeip_pointwise.hpp", "pdeip_sparse_plan.hpp", "pdeip_seeds_plan.hpp"],
     "pdeip_ccl.hip": ["pdeip_ccl.hpp", "pdeip_ccl_plan.hpp"],
     "pdeip_flowviz.hip": ["pdeip_flowviz.hpp", "pdeip_reduce.hpp"],
-    "pdeip_crosscheck.hip": ["pdeip_crosscheck.hpp", "pdeip_sym_warp.hpp", "pdeip_reduce.hpp"],
+    "pdeip_crosscheck.hip": ["pdeip_crosscheck.hpp", "pdeip_sym_warp.hpp", "pdeip_reduce.hpp", "pdeip_bilinear.hpp"],
     "pdeip_inpaint.hip": ["pdeip_inpaint.hpp", "pdeip_pyr.hpp", "pdeip_pointwise.hpp"],
+    "pdeip_interp.hip": ["pdeip_interp.hpp", "pdeip_bilinear.hpp"],
 }
 # -ffp-contract=off is part of the parity contract (the reference is FMA-free C).
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]

@@ -188,6 +188,11 @@ SIGNATURES = {
     "pdeip_inpaint_merge_dev": [_P, _P, _P, _I, _I, _I, _P, _P],
     "pdeip_tv_inpaint4_dev": [_P, _P, _I, _I, _I, _P, _I, _P, _P, _P],
     "pdeip_tv_inpaint4": [_P, _I, _I, _I, _P, _I, _P, _P, _P],
+    # frame interpolation (csrc/pdeip_interp.hip)
+    "pdeip_flow_splat_dev": [_P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_double, _P, _P, _P],
+    "pdeip_interp_blend_dev": [_P, _P, _P, _I, _P, _P, _P, _P, _I, _I, ctypes.c_double, _P, _P],
+    "pdeip_flow_interpolate_dev": [_P, _P, _P, _I, _P, _P, _P, _P, _I, _I, ctypes.c_double, _P, _P, _P, _P, _P],
+    "pdeip_flow_interpolate": [_P, _P, _I, _P, _P, _P, _P, _I, _I, ctypes.c_double, _P, _P, _P, _P, _P],
     # library state
     "pdeip_set_mode": [_I],
     "pdeip_get_mode": [],

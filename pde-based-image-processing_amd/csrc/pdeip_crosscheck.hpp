@@ -15,6 +15,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "pdeip_bilinear.hpp"
 #include "pdeip_reduce.hpp"
 #include "pdeip_sym_warp.hpp"
 
@@ -89,15 +90,6 @@ __global__ __launch_bounds__(BLOCK) void k_disp_crosscheck(const float *D0, cons
         fold_workgroup(kept, defined, sum, largest, partials, (size_t)gridDim.x * gridDim.y, (size_t)blockIdx.y * gridDim.x + blockIdx.x);
 }
 
-// B(A) at the 0-based taps (r0, c0), (r0, c1), (r1, c0), (r1, c1): s along x (columns), t along y (rows), in exactly this order.
-__device__ __forceinline__ double bilinear(const float *__restrict__ A, int nrows, int r0, int r1, int c0, int c1, double s, double t)
-{
-    const size_t a0 = (size_t)c0 * nrows, a1 = (size_t)c1 * nrows;
-    const double top = (double)A[a0 + r0] * (1.0 - s) + (double)A[a1 + r0] * s;
-    const double bot = (double)A[a0 + r1] * (1.0 - s) + (double)A[a1 + r1] * s;
-    return top * (1.0 - t) + bot * t;
-}
-
 // Grid: pixel_grid(nrows, ncols, 1).  Needs nrows, ncols >= 2.  Ub, Vb are gathered and are never an output.
 __global__ __launch_bounds__(BLOCK) void k_flow_crosscheck(const float *__restrict__ Uf, const float *__restrict__ Vf, const float *__restrict__ Ub,
                                                             const float *__restrict__ Vb, int nrows, int ncols, double a, double b,
@@ -110,14 +102,10 @@ __global__ __launch_bounds__(BLOCK) void k_flow_crosscheck(const float *__restri
         const double uf = (double)Uf[pos], vf = (double)Vf[pos];
         const double xq = (double)(j + 1) + uf, yq = (double)(i + 1) + vf;
         double ub = __longlong_as_double(0x7ff8000000000000LL), vb = ub;
-        if (xq >= 1.0 && xq <= (double)ncols && yq >= 1.0 && yq <= (double)nrows) { // a NaN query fails
-            double j0 = floor(xq), i0 = floor(yq);
-            if (j0 > (double)(ncols - 1)) j0 = (double)(ncols - 1); // xq == ncols: the last column itself (s = 1)
-            if (i0 > (double)(nrows - 1)) i0 = (double)(nrows - 1);
-            const double s = xq - j0, t = yq - i0;
-            const int c0 = (int)j0 - 1, c1 = min(c0 + 1, ncols - 1), r0 = (int)i0 - 1, r1 = min(r0 + 1, nrows - 1);
-            ub = bilinear(Ub, nrows, r0, r1, c0, c1, s, t);
-            vb = bilinear(Vb, nrows, r0, r1, c0, c1, s, t);
+        BilinearTaps T;
+        if (bilinear_taps(xq, yq, nrows, ncols, &T)) { // csrc/pdeip_bilinear.hpp: the in-range rule and the clamps
+            ub = bilinear(Ub, nrows, T);
+            vb = bilinear(Vb, nrows, T);
         }
         const double ru = uf + ub, rv = vf + vb;
         const double e = ru * ru + rv * rv;

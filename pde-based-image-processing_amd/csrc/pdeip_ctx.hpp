@@ -21,7 +21,7 @@
 
 namespace pdeip {
 
-enum { WS_AUX0 = 0, WS_AUX1, WS_PING, WS_ARENA, WS_CTL, WS_ORDER, WS_ALR, WS_ALR_T, WS_TV, WS_SMALL, WS_MAIL, WS_PACK, WS_DRIVER, WS_LEX, WS_LS, WS_RANSAC, WS_SEG_STAGE, WS_SEG, WS_SEG_RC, WS_CCL, WS_SEEDS, WS_SELECT, WS_GAC, WS_RANSAC_BATCH, WS_FLOWVIZ, WS_CROSSCHECK, WS_NSLOT };
+enum { WS_AUX0 = 0, WS_AUX1, WS_PING, WS_ARENA, WS_CTL, WS_ORDER, WS_ALR, WS_ALR_T, WS_TV, WS_SMALL, WS_MAIL, WS_PACK, WS_DRIVER, WS_LEX, WS_LS, WS_RANSAC, WS_SEG_STAGE, WS_SEG, WS_SEG_RC, WS_CCL, WS_SEEDS, WS_SELECT, WS_GAC, WS_RANSAC_BATCH, WS_FLOWVIZ, WS_CROSSCHECK, WS_INTERP, WS_NSLOT };
 
 constexpr int MAX_DEVICES = 16;
 
@@ -142,6 +142,9 @@ inline dim3 pixel_grid(int nrows, int ncols, int nz) { return dim3((unsigned)((n
 // The sparse driver's D pyramid on device planes (pdeip_sparse.hip): P[0] = nanmed(D), P[k] = nanmed(resize_cubic(nanmed(P[k-1]))), 3K - 2
 // launches on s.  rc: rows, cols per scale [2K]; t1 / t2: a plane of scale 1 / scale 2 (sparse::layout of pdeip_sparse_plan.hpp).
 int sparse_pyramid_dev(hipStream_t s, const float *D, const int *rc, int K, float *const *P, float *t1, float *t2);
+
+// The refusals of pdeip_tv_inpaint4_dev for a frame and a parameter struct, without a launch (pdeip_inpaint.hip).
+int inpaint_check_params(const char *who, int nrows, int ncols, int frames, const pdeip_inpaint_params *prm);
 
 // Makes group[0] (or `device`) the current HIP device; reads the environment knobs on first use.
 int use_device();

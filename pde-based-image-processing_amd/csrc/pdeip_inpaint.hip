@@ -108,6 +108,15 @@ int resolve(const char *who, const void *D, int nrows, int ncols, int frames, co
 
 } // namespace
 
+// What pdeip_tv_inpaint4(_dev) would refuse for this frame and these parameters, for a chain that wants to refuse before its first
+// launch (pdeip_flow_interpolate): no pointer is dereferenced and no HIP call made.
+int pdeip::inpaint_check_params(const char *who, int nrows, int ncols, int frames, const pdeip_inpaint_params *prm)
+{
+    static const float plane = 0.0f;
+    Resolved p;
+    return resolve(who, &plane, nrows, ncols, frames, nullptr, 0, prm, &plane, &p);
+}
+
 extern "C" int pdeip_nan_resize_dev(void *stream, const float *in, int nrows, int ncols, int nframes, int nrows_out, int ncols_out, double cover,
                                     float *out)
 {

@@ -971,3 +971,102 @@ def tv_inpaint4(D, guide=None, out=None, filled_out=None, mode=None, **param):
         if mode is not None:
             capi.set_mode(old)
     return out
+
+
+# ---- frame interpolation from a computed flow (csrc/pdeip_interp.hip) ----
+class InterpParams(ctypes.Structure):
+    """pdeip_interp_params: a, b the cross-checks' thresholds, use_costs 0 = the lowest index wins a target, fill the hole filling's
+    parameters (InpaintParams; kept alive by this object).  Any other keyword goes to the hole filling."""
+    _fields_ = [("a", ctypes.c_double), ("b", ctypes.c_double), ("use_costs", ctypes.c_int), ("fill", ctypes.c_void_p)]
+
+    @classmethod
+    def make(cls, **param):
+        s = cls(a=0.01, b=0.5, use_costs=1, fill=None)
+        for k in ("a", "b", "use_costs"):
+            if k in param:
+                setattr(s, k, type(getattr(s, k))(param.pop(k)))
+        s._fill = None
+        if param:
+            try:
+                s._fill = InpaintParams.make(**param)
+            except capi.PdeipError as exc:
+                raise capi.PdeipError(exc.code, str(exc).replace("tv_inpaint4", "flow_interpolate")) from None
+            s.fill = ctypes.addressof(s._fill)
+        return s
+
+
+def _images(I0, I1, like, who):
+    """Channels of the two frames [(C,) ncols, nrows] on the frame of `like`."""
+    _chk(I0, I1)
+    if I0.shape != I1.shape or I0.shape[-2:] != like.shape[-2:]:
+        raise capi.PdeipError(capi.PDEIP_ERR_ARG, "%s: the frames are %s and %s but the flow is %s"
+                              % (who, tuple(I0.shape), tuple(I1.shape), tuple(like.shape)))
+    return _dims(I0)[2]
+
+
+def _flow_planes(who, first, *rest):
+    fields = (first,) + tuple(t for t in rest if t is not None)
+    _chk(*fields)
+    if first.dim() != 2 or any(t.shape != first.shape for t in fields):
+        raise capi.PdeipError(capi.PDEIP_ERR_ARG, "%s: the flow and mask planes must be planes [ncols, nrows] of one shape" % who)
+
+
+def flow_splat(Uf, Vf, t=0.5, I0=None, I1=None, Ut_out=None, Vt_out=None, cost_out=None, cost=True):
+    """The resident flow (Uf, Vf) of frame 0 -> 1 carried forward to time t (pdeip_flow_splat_dev): every target takes the source
+    of the lowest photo-consistency cost |I0 - I1(x + f)| (frames [(C,) ncols, nrows]; without frames the lowest index).  Returns
+    (Ut, Vt, cost): NaN where nothing landed; cost None with cost=False unless handed in.  Nothing is read back."""
+    _flow_planes("flow_splat", Uf, Vf)
+    if (I0 is None) != (I1 is None):
+        raise capi.PdeipError(capi.PDEIP_ERR_ARG, "flow_splat: I0 and I1 must both be given or both be None")
+    channels = 0 if I0 is None else _images(I0, I1, Uf, "flow_splat")
+    nrows, ncols, _ = _dims(Uf)
+    Ut_out = _out_plane(Uf, Ut_out, True, "flow_splat: Ut_out")
+    Vt_out = _out_plane(Uf, Vt_out, True, "flow_splat: Vt_out")
+    cost_out = _out_plane(Uf, cost_out, cost, "flow_splat: cost_out")
+    capi.call("pdeip_flow_splat_dev", _stream(), *_p(Uf, Vf), _ptr(I0), _ptr(I1), channels, nrows, ncols, float(t), *_p(Ut_out, Vt_out),
+              _ptr(cost_out))
+    return Ut_out, Vt_out, cost_out
+
+
+def interp_blend(I0, I1, Ut, Vt, t=0.5, M0=None, M1=None, It_out=None, source_out=None, source=True):
+    """The picture at time t along the dense resident flow (Ut, Vt) given at t (pdeip_interp_blend_dev); M0, M1: the masks of
+    flow_crosscheck for the forward flow in frame 0 and the backward flow in frame 1, or None.  Returns (It, source): It like I0,
+    source 0 neither frame, 1 frame 0, 2 frame 1, 3 both (None with source=False unless handed in).  Nothing is read back."""
+    _flow_planes("interp_blend", Ut, Vt, M0, M1)
+    if (M0 is None) != (M1 is None):
+        raise capi.PdeipError(capi.PDEIP_ERR_ARG, "interp_blend: M0 and M1 must both be given or both be None")
+    channels = _images(I0, I1, Ut, "interp_blend")
+    nrows, ncols, _ = _dims(Ut)
+    It_out = _out_plane(I0, It_out, True, "interp_blend: It_out")
+    source_out = _out_plane(Ut, source_out, source, "interp_blend: source_out")
+    capi.call("pdeip_interp_blend_dev", _stream(), *_p(I0, I1), channels, *_p(Ut, Vt), _ptr(M0), _ptr(M1), nrows, ncols, float(t),
+              It_out.data_ptr(), _ptr(source_out))
+    return It_out, source_out
+
+
+def flow_interpolate(I0, I1, Uf, Vf, Ub=None, Vb=None, t=0.5, It_out=None, Ut_out=None, Vt_out=None, source_out=None, flow=True, source=True,
+                     mode=None, **param):
+    """The whole resident chain (pdeip_flow_interpolate_dev): the cross-checks of (Uf, Vf) against (Ub, Vb) if the backward flow is
+    given, the splat to time t, the hole filling and the blend.  Returns (It, Ut, Vt, source): the frame at t like I0, the filled flow
+    at t and the source plane (None with flow=False / source=False unless handed in).  mode: the ordering of the hole filling's solver
+    calls (None: the library's current mode); param: a, b, use_costs and tv_inpaint4's.  Nothing is read back."""
+    _flow_planes("flow_interpolate", Uf, Vf, Ub, Vb)
+    if (Ub is None) != (Vb is None):
+        raise capi.PdeipError(capi.PDEIP_ERR_ARG, "flow_interpolate: Ub and Vb must both be given or both be None")
+    channels = _images(I0, I1, Uf, "flow_interpolate")
+    nrows, ncols, _ = _dims(Uf)
+    It_out = _out_plane(I0, It_out, True, "flow_interpolate: It_out")
+    Ut_out = _out_plane(Uf, Ut_out, flow, "flow_interpolate: Ut_out")
+    Vt_out = _out_plane(Uf, Vt_out, flow, "flow_interpolate: Vt_out")
+    source_out = _out_plane(Uf, source_out, source, "flow_interpolate: source_out")
+    prm = InterpParams.make(**param)
+    old = capi.get_mode()
+    if mode is not None:
+        capi.set_mode(mode)
+    try:
+        capi.call("pdeip_flow_interpolate_dev", _stream(), *_p(I0, I1), channels, *_p(Uf, Vf), _ptr(Ub), _ptr(Vb), nrows, ncols, float(t),
+                  ctypes.addressof(prm), It_out.data_ptr(), _ptr(Ut_out), _ptr(Vt_out), _ptr(source_out))
+    finally:
+        if mode is not None:
+            capi.set_mode(old)
+    return It_out, Ut_out, Vt_out, source_out

@@ -82,6 +82,38 @@ def _apriori_pyramid(field, shapes, scl_factor):
     return out
 
 
+def _flow_llin_planes(level_cls, f0, f1, fstTerm, sndTerm, p, mode, Us=None, Vs=None, scales=None):
+    """The level loop of the llin flow drivers on resident frames f0, f1 [C, ncols, nrows] (already ./255): the flow as two resident
+    planes [ncols, nrows]; nothing is downloaded."""
+    P0, P1 = pyramid.build_dev(f0, f1, p["scl_factor"], 20, max_scales=scales)
+    level = level_cls(p, mode=mode)
+    U = _zeros_like_plane(P0[-1])
+    V = torch.zeros_like(U)
+    shapes = [(t.shape[-1], t.shape[-2]) for t in P0]
+    ap = {}
+    for name, field in (("Us", Us), ("Vs", Vs)):
+        if field is not None:
+            ap[name] = _apriori_pyramid(field, shapes, p["scl_factor"])
+    if "Us" in ap:   # U = USap{scales} (:178): MATLAB's double array; here its float32 rounding, as in the disparity driver
+        U = dev.to_device(ap["Us"][-1].astype(np.float32))
+    if "Vs" in ap:
+        V = dev.to_device(ap["Vs"][-1].astype(np.float32))
+    for scl in range(len(P0) - 1, -1, -1):
+        d0, d1 = P0[scl], P1[scl]
+        (a0, a1), (b0, b1) = _terms(d0, d1, fstTerm, sndTerm)
+        args = (a0, a1, U, V) + ((d0,) if level_cls is fl.FlowAdLevel else ()) + (b0, b1)
+        kw = {}
+        if ap:
+            on_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a.T)).to(U.device)
+            kw = dict(Us=on_dev(ap["Us"][scl]) if "Us" in ap else None, Vs=on_dev(ap["Vs"][scl]) if "Vs" in ap else None,
+                      as_diff=2.0 * p["scl_factor"] ** scl, u_double=(scl == len(P0) - 1))
+        U, V = level.run(*args, **kw)
+        if scl > 0:
+            cols, rows = P0[scl - 1].shape[-2:]
+            U, V = _up(U, 1.0 / p["scl_factor"], rows, cols), _up(V, 1.0 / p["scl_factor"], rows, cols)
+    return U, V
+
+
 def _flow_llin(level_cls, Iin, channels, fstTerm, sndTerm, defaults, mode, param):
     param = dict(param)
     graph = bool(param.pop("graph", False))   # exact order too since round 3: the walkers' schedule table is built on the stream
@@ -93,33 +125,7 @@ def _flow_llin(level_cls, Iin, channels, fstTerm, sndTerm, defaults, mode, param
         raise ValueError("graph=True replays a captured run: not with a-priori fields")
 
     def device_part(f0, f1):
-        P0, P1 = pyramid.build_dev(f0, f1, p["scl_factor"], 20, max_scales=scales)
-        level = level_cls(p, mode=mode)
-        U = _zeros_like_plane(P0[-1])
-        V = torch.zeros_like(U)
-        shapes = [(t.shape[-1], t.shape[-2]) for t in P0]
-        ap = {}
-        for name, field in (("Us", Us), ("Vs", Vs)):
-            if field is not None:
-                ap[name] = _apriori_pyramid(field, shapes, p["scl_factor"])
-        if "Us" in ap:   # U = USap{scales} (:178): MATLAB's double array; here its float32 rounding, as in the disparity driver
-            U = dev.to_device(ap["Us"][-1].astype(np.float32))
-        if "Vs" in ap:
-            V = dev.to_device(ap["Vs"][-1].astype(np.float32))
-        for scl in range(len(P0) - 1, -1, -1):
-            d0, d1 = P0[scl], P1[scl]
-            (a0, a1), (b0, b1) = _terms(d0, d1, fstTerm, sndTerm)
-            args = (a0, a1, U, V) + ((d0,) if level_cls is fl.FlowAdLevel else ()) + (b0, b1)
-            kw = {}
-            if ap:
-                on_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a.T)).to(U.device)
-                kw = dict(Us=on_dev(ap["Us"][scl]) if "Us" in ap else None, Vs=on_dev(ap["Vs"][scl]) if "Vs" in ap else None,
-                          as_diff=2.0 * p["scl_factor"] ** scl, u_double=(scl == len(P0) - 1))
-            U, V = level.run(*args, **kw)
-            if scl > 0:
-                cols, rows = P0[scl - 1].shape[-2:]
-                U, V = _up(U, 1.0 / p["scl_factor"], rows, cols), _up(V, 1.0 / p["scl_factor"], rows, cols)
-        return U, V
+        return _flow_llin_planes(level_cls, f0, f1, fstTerm, sndTerm, p, mode, Us, Vs, scales)
 
     f0, f1 = dev.div_scalar(I0, 255.0), dev.div_scalar(I1, 255.0)
     if graph:   # the few thousand launches of the run replayed as one HIP graph (graphs.py); same kernels, same results
@@ -975,3 +981,98 @@ def capi_TVinpaint4(D, guide=None, mode=capi.MODE_EXACT_ORDER, return_filled=Fal
         capi.set_mode(old)
     shape = (lambda a: a if d.ndim == 3 else a[:, :, 0])
     return (shape(out), shape(filled)) if return_filled else shape(out)
+
+
+# ---- frame interpolation: the picture between two frames, from a computed flow (include/pdeip.h; this library's own driver) ----
+def _interp_param(who, param):
+    """(mode, InterpParams) of a driver's keyword parameters: mode, a, b, use_costs and TVinpaint4's for the hole filling."""
+    param = dict(param)
+    mode = param.pop("mode", capi.MODE_EXACT_ORDER)
+    fill = {k: param.pop(k) for k in list(param) if k in INPAINT_DEFAULTS}
+    unknown = set(param) - {"a", "b", "use_costs"}
+    if unknown:
+        raise ValueError("%s: unknown parameter %s" % (who, sorted(unknown)))
+    _inpaint_param(who, fill)
+    for k in ("a", "b"):
+        if k in param:
+            param[k] = _threshold(who, k, param[k])
+    return mode, dict(param, **fill)
+
+
+def _time(who, t):
+    t = float(t)
+    if not 0.0 < t < 1.0:
+        raise ValueError("%s: t must lie strictly between 0 and 1 (got %r)" % (who, t))
+    return t
+
+
+def flow_interpolate(I0, I1, U, V, Ub=None, Vb=None, t=0.5, return_flow=False, return_source=False, **param):
+    """The frame at time t between I0 and I1 [rows, cols(, channels)] from the flow (U, V) of frame 0 -> 1, in one
+    pdeip_flow_interpolate call (include/pdeip.h): the flow is carried forward to t (the most photo-consistent source wins a
+    pixel), its holes are filled by TV inpainting, and both frames are sampled along it and blended.  With the backward flow
+    (Ub, Vb) of frame 1 -> 0 the two forward-backward checks decide at an occlusion which frame alone is shown.  param: mode, a 0.01,
+    b 0.5, use_costs 1 and TVinpaint4's.  Returns It, with return_flow also the filled flow at t as [rows, cols, 2], with
+    return_source also the plane 0 neither / 1 frame 0 / 2 frame 1 / 3 both."""
+    who = "flow_interpolate"
+    mode, prm_kw = _interp_param(who, param)
+    t = _time(who, t)
+    if (Ub is None) != (Vb is None):
+        raise ValueError("%s: Ub and Vb must both be given or both be None" % who)
+    i0, i1 = np.asarray(I0, dtype=np.float32), np.asarray(I1, dtype=np.float32)
+    if i0.ndim not in (2, 3) or i0.shape != i1.shape:
+        raise ValueError("%s: I0 and I1 must be [rows, cols(, channels)] arrays of one shape" % who)
+    names = "U, V" + (", Ub and Vb" if Ub is not None else "")
+    planes = _same_planes(who, names, (U, V) + ((Ub, Vb) if Ub is not None else ()))
+    if planes[0].shape != i0.shape[:2]:
+        raise ValueError("%s: the flow is %s but the frames are %s" % (who, planes[0].shape, i0.shape[:2]))
+    f0, f1 = _f_single(i0), _f_single(i1)
+    rows, cols, C = f0.shape
+    It = np.zeros((rows, cols, C), np.float32, order="F")
+    Ut, Vt = ((np.zeros((rows, cols), np.float32, order="F") for _ in range(2)) if return_flow else (None, None))
+    src = np.zeros((rows, cols), np.float32, order="F") if return_source else None
+    prm = dev.InterpParams.make(**prm_kw)
+    ptr = lambda a: None if a is None else a.ctypes.data
+    old = capi.get_mode()
+    capi.set_mode(mode)
+    try:
+        capi.call("pdeip_flow_interpolate", f0.ctypes.data, f1.ctypes.data, C, planes[0].ctypes.data, planes[1].ctypes.data,
+                  ptr(planes[2]) if Ub is not None else None, ptr(planes[3]) if Ub is not None else None, rows, cols, t,
+                  ctypes.addressof(prm), It.ctypes.data, ptr(Ut), ptr(Vt), ptr(src))
+    finally:
+        capi.set_mode(old)
+    out = (It if i0.ndim == 3 else It[:, :, 0],)
+    if return_flow:
+        out += (np.stack([Ut, Vt], axis=2),)
+    if return_source:
+        out += (src,)
+    return out[0] if len(out) == 1 else out
+
+
+def interpolate_frames(Iin, channels, t=(0.5,), mode=capi.MODE_EXACT_ORDER, fstTerm="rgb", sndTerm="none", return_flows=False, **param):
+    """In-between frames of Iin = cat(3, frame0, frame1): FlowEminND_llin_2D_v10's level loop forward and with the frames swapped,
+    then the chain of flow_interpolate for every t, all on the device with one download at the end.  param: the flow driver's
+    parameters; the chain's go in interp=dict(...).  Returns the list of frames [rows, cols(, channels)], one per t (values on Iin's
+    scale); with return_flows also the forward and the backward flow as [rows, cols, 2] arrays."""
+    who = "interpolate_frames"
+    param = dict(param)
+    interp = dict(param.pop("interp", None) or {})
+    interp.pop("mode", None)
+    _, prm_kw = _interp_param(who, interp)
+    times = [_time(who, x) for x in (t if np.ndim(t) else (t,))]
+    scales = param.pop("scales", None)
+    p = dict(ND_DEFAULTS, **param)
+    p["sndTerm"] = sndTerm.lower()
+    I0, I1 = _frames(Iin, channels)
+    f0, f1 = dev.div_scalar(I0, 255.0), dev.div_scalar(I1, 255.0)
+    Uf, Vf = _flow_llin_planes(fl.FlowLlinLevel, f0, f1, fstTerm, sndTerm, p, mode, scales=scales)
+    Ub, Vb = _flow_llin_planes(fl.FlowLlinLevel, f1, f0, fstTerm, sndTerm, p, mode, scales=scales)
+    Uf, Vf, Ub, Vb = (x.contiguous() for x in (Uf, Vf, Ub, Vb))
+    frames = [dev.flow_interpolate(I0, I1, Uf, Vf, Ub, Vb, t=x, flow=False, source=False, mode=mode, **prm_kw)[0] for x in times]
+    dev.sync_check()
+    out = [dev.to_matlab(f) for f in frames]
+    if channels == 1:
+        out = [f[:, :, 0] for f in out]
+    if return_flows:
+        both = lambda a, b: np.stack([dev.to_matlab(a), dev.to_matlab(b)], axis=2)
+        return out, both(Uf, Vf), both(Ub, Vb)
+    return out
