@@ -107,5 +107,5 @@ def flow_errors(U, V, Ut, Vt, mask=None):
     e64, a64 = epe.T[counted.T], ang.T[counted.T]
     n = int(counted.sum())
     return dict(epe=np.asfortranarray(epe.astype(F32)), ang=np.asfortranarray(ang.astype(F32)), counted=counted, epe64=e64, ang64=a64,
-                ang_plane64=ang, count=n, mean_epe=math.fsum(e64) / n if n else math.nan, mean_ang=math.fsum(a64) / n if n else math.nan,
+                epe_plane64=epe, ang_plane64=ang, count=n, mean_epe=math.fsum(e64) / n if n else math.nan, mean_ang=math.fsum(a64) / n if n else math.nan,
                 max_epe=float(e64.max()) if n else math.nan)

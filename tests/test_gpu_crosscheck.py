@@ -6,7 +6,8 @@ Every case runs on planes carved at a 4-byte offset as well as on 16-byte aligne
   mask, sparse, diff / err   bit for bit (NaN positions, and the bits of every other value): correctly rounded IEEE operations on
                              identical inputs in one order, plus one rounding to float32
   kept, defined, largest     bit for bit (integers in doubles; a maximum is exact in any order)
-  mean                       within 2 defined 2^-53 relative of math.fsum: two summation orders of non-negative terms
+  mean                       within 2 defined 2^-53 relative of math.fsum: two summation orders of non-negative terms; and equal in
+                             its bits to the sum in the documented order (reduce_tree_ref.py, pinned by test_reduce_tree_ref.py)
   launches                   2 with stats_out, 1 without
   the inputs                 unchanged; sparse_out aliasing D0 gives the same bits; two calls give identical statistics; the host forms
                              equal the _dev forms byte for byte
@@ -22,6 +23,7 @@ import pytest
 
 import crosscheck_cases as cc
 import crosscheck_ref as cr
+from flow_gpu_util import carve, check_stats, same_f32
 
 pytestmark = pytest.mark.gpu
 F32, F64 = np.float32, np.float64
@@ -33,42 +35,6 @@ def _dev():
 
 def _drv():
     return importlib.import_module("pde-based-image-processing_amd.drivers")
-
-
-def carve(a, offset):
-    """The plane on the device, [ncols, nrows]; offset 1: at 4 bytes past a 16-byte boundary."""
-    import torch
-
-    t = _dev().to_device(a)
-    if not offset:
-        assert t.data_ptr() % 16 == 0
-        return t
-    buf = torch.empty(t.numel() + 4, dtype=torch.float32, device=t.device)
-    assert buf.data_ptr() % 16 == 0
-    out = buf[1:1 + t.numel()].view(t.shape)
-    out.copy_(t)
-    assert out.data_ptr() % 16 == 4 and out.is_contiguous()
-    return out
-
-
-def same_f32(got, want, what):
-    assert got.shape == want.shape and got.dtype == F32, what
-    gn, wn = np.isnan(got), np.isnan(want)
-    assert np.array_equal(gn, wn), "%s: NaN at %d pixels where the restatement has none or the reverse" % (what, int((gn != wn).sum()))
-    bad = got[~gn].view(np.uint32) != want[~wn].view(np.uint32)
-    assert not bad.any(), "%s: %d values differ in their bits" % (what, int(bad.sum()))
-
-
-def check_stats(stats, want, what):
-    assert stats[0] == want["kept"] and stats[1] == want["defined"], "%s: counts %r, want %d / %d" % (what, stats[:2], want["kept"], want["defined"])
-    if want["defined"] == 0:
-        assert np.isnan(stats[2:]).all(), what
-        return
-    assert np.float64(stats[3]).view(np.uint64) == np.float64(want["max"]).view(np.uint64), "%s: largest %r != %r" % (what, stats[3], want["max"])
-    bound = 2.0 * want["defined"] * 2.0 ** -53
-    rel = abs(stats[2] - want["mean"]) / want["mean"] if want["mean"] else abs(stats[2])
-    print("%s: kept %d of %d defined, mean off by %.3g relative (bound %.3g)" % (what, want["kept"], want["defined"], rel, bound))
-    assert rel <= bound, what
 
 
 def _launches(pdeip):
@@ -306,6 +272,7 @@ def test_yosemite_forward_backward(pdeip, oracle):
     assert set(np.unique(m)) <= {0.0, 1.0} and float(m.astype(F64).sum()) == stats[0]
     want = cr.flow_crosscheck(*[dev.to_matlab(t) for t in (gUf, gVf, gUb, gVb)], 0.01, 0.5)
     assert np.array_equal(m, want["mask"]) and stats[1] == want["defined"]
+    check_stats(stats, want, "yosemite forward-backward")
     assert masked[0] == int(((m != 0) & np.isfinite(Ut) & np.isfinite(Vt)).sum())
     print("yosemite forward-backward, a 0.01 b 0.5: kept %d of %d pixels (%.3f), %d defined, mean |f + b| %.4f, largest %.4f; mean endpoint "
           "error %.4f over the kept pixels, %.4f over all %d"

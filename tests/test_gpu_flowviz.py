@@ -11,7 +11,10 @@ the last pixel and the workgroup seams, nowhere else; -0.0 components; the all-z
   uint8          round(255 ref); 1 off only where 255 ref is within 255 * 2^-24 of a half-integer
   errors         the endpoint error plane, the count and the largest endpoint error bit for bit (correctly rounded IEEE operations on
                  identical inputs); the mean endpoint error within 2 n 2^-53 relative of math.fsum (two summation orders of
-                 non-negative terms); the angular error within ANG_TOL relative (only the two libraries' acos differ)
+                 non-negative terms); the angular error within ANG_TOL relative (only the two libraries' acos differ).  The count,
+                 the mean endpoint error and the largest are also equal in their bits to the sum in the documented order
+                 (reduce_tree_ref.py, pinned by test_reduce_tree_ref.py); the mean angular error lies within ANG_TOL plus the two
+                 trees' own rounding of it, 2 (ntiles + 18) 2^-53: its summands are not the same numbers on the two sides
 """
 import importlib
 import math
@@ -20,19 +23,14 @@ import numpy as np
 import pytest
 
 import flowviz_ref as fr
+from flow_gpu_util import (ANG_TOL, RGB_TOL, _bits, _same_max, carve, check_errors, check_rgb, exact_mask, run_errors)
+from flow_gpu_util import error_tree_of as tree_of
 
 pytestmark = pytest.mark.gpu
 F32, F64 = np.float32, np.float64
 
 SHAPES = [(1, 1), (1, 7), (7, 1), (5, 300), (257, 3), (37, 53), (270, 480)]
 FIELDS = ["normal", "nan_u", "nan_v", "inf_u", "inf_v", "neg_zero", "zero", "all_nan"]
-RGB_TOL = 2.0 ** -24
-# The relative difference between the device's double acos and the host libm's, argument identical.  No ulp statement for the device
-# math library ships with the toolchain, so the figure was measured once on the MI355X (23 205 pixels of these cases'
-# fields, random, nearly parallel and nearly opposite pairs, each pixel's float64 value read through a one-pixel mask): 2.48e-16 =
-# 2^-51.84, a little over one ulp.  The bound is four times that (another libm version has to pass too), never looser than 2^-40.
-ANG_MEASURED = 2.48e-16
-ANG_TOL = min(4.0 * ANG_MEASURED, 2.0 ** -40)
 
 
 def _dev():
@@ -83,37 +81,6 @@ def field(shape, kind, seed=11):
     return U, V
 
 
-def carve(a, offset):
-    """The plane on the device, [ncols, nrows]; offset 1: at 4 bytes past a 16-byte boundary."""
-    import torch
-
-    t = _dev().to_device(a)
-    if not offset:
-        assert t.data_ptr() % 16 == 0
-        return t
-    buf = torch.empty(t.numel() + 4, dtype=torch.float32, device=t.device)
-    assert buf.data_ptr() % 16 == 0
-    out = buf[1:1 + t.numel()].view(t.shape)
-    out.copy_(t)
-    assert out.data_ptr() % 16 == 4 and out.is_contiguous()
-    return out
-
-
-def _bits(x):
-    return np.float64(x).view(np.uint64)
-
-
-def _same_max(got, want, what):
-    assert (math.isnan(got) and math.isnan(want)) or _bits(got) == _bits(want), "%s: maxvalue %r != %r" % (what, got, want)
-
-
-def check_rgb(got, ref32, exact, what):
-    assert got.shape == ref32.shape and got.dtype == F32, what
-    diff = np.abs(got.astype(F64) - ref32.astype(F64))
-    assert not np.isnan(diff).any() and diff.max() <= RGB_TOL, "%s: float rgb off by %.3g" % (what, diff.max())
-    assert np.array_equal(got[exact], ref32[exact]), "%s: invalid / zero-magnitude pixels differ" % what
-
-
 def check_u8(got, ref32, ref64, what):
     want = fr.to_uint8(ref32)
     assert got.shape == want.shape and got.dtype == np.uint8, what
@@ -122,16 +89,6 @@ def check_u8(got, ref32, ref64, what):
         y = 255.0 * ref64[off]
         assert np.all(np.abs(got[off].astype(np.int64) - want[off].astype(np.int64)) == 1), what
         assert np.all(np.abs(y - (np.floor(y) + 0.5)) <= 255.0 * RGB_TOL), "%s: uint8 differs away from a half-integer" % what
-
-
-def exact_mask(U, V, valid, border=0):
-    """Pixels of the picture that must match to the bit: the flow's invalid and zero-magnitude ones."""
-    inner = ~valid | ((U == 0) & (V == 0))
-    rows, cols = U.shape
-    m = np.zeros((rows + 2 * border, cols + 2 * border), bool)
-    o = max(border - 1, 0)
-    m[o:o + rows, o:o + cols] = inner
-    return m
 
 
 def run_color(pdeip, U, V, offset, maxvalue=None, border=0):
@@ -246,55 +203,6 @@ def mask_for(shape, kind):
     return m
 
 
-def ulp_mid_ok(got32, ref32, ref64, tol, what):
-    """got32 equals ref32 up to the one float32 rounding: where they differ they are neighbours and the float64 value lies within
-    tol (relative) of the midpoint between them."""
-    off = got32 != ref32
-    off &= ~(np.isnan(got32) & np.isnan(ref32))
-    if off.any():
-        g, r, x = got32[off].astype(F64), ref32[off].astype(F64), ref64[off]
-        assert np.all(np.abs(g - r) <= np.spacing(np.maximum(np.abs(got32[off]), np.abs(ref32[off]))).astype(F64)), what + ": not neighbours"
-        assert np.all(np.abs(x - 0.5 * (g + r)) <= tol * np.abs(x)), what + ": differs away from a rounding boundary"
-
-
-def run_errors(pdeip, planes, mask, offset):
-    import torch
-
-    dev = _dev()
-    ts = [carve(p, offset) for p in planes]
-    tm = None if mask is None else carve(mask, offset)
-    epe, ang, stats = dev.flow_errors(*ts, mask=tm)
-    assert pdeip.capi.load().pdeip_last_launch_count() == 2
-    epe2, ang2, stats2 = dev.flow_errors(*ts, mask=tm, epe_out=torch.full_like(ts[0], 5.0), ang_out=torch.full_like(ts[0], 5.0))
-    torch.cuda.synchronize()
-    assert pdeip.capi.last_error() == ""
-    out = dev.to_matlab(epe), dev.to_matlab(ang), stats.cpu().numpy()
-    assert dev.to_matlab(epe2).tobytes() == out[0].tobytes() and dev.to_matlab(ang2).tobytes() == out[1].tobytes()
-    assert stats2.cpu().numpy().tobytes() == out[2].tobytes(), "two calls differ"
-    return out
-
-
-def check_errors(got, want, what):
-    epe, ang, stats = got
-    n = want["count"]
-    assert np.array_equal(np.isnan(epe), ~want["counted"]) and np.array_equal(np.isnan(ang), ~want["counted"]), what + ": excluded pixels differ"
-    ok = want["counted"]
-    assert np.array_equal(epe[ok].view(np.uint32), want["epe"][ok].view(np.uint32)), what + ": endpoint error bits differ"
-    assert stats[0] == n, what
-    if n == 0:
-        assert np.isnan(stats[1:]).all(), what
-        return
-    assert _bits(stats[3]) == _bits(want["max_epe"]), what
-    bound = 2.0 * n * 2.0 ** -53
-    rel_e = abs(stats[1] - want["mean_epe"]) / want["mean_epe"] if want["mean_epe"] else abs(stats[1])
-    rel_a = abs(stats[2] - want["mean_ang"]) / want["mean_ang"] if want["mean_ang"] else abs(stats[2])
-    print("%s: n %d, mean endpoint error off by %.3g relative (bound %.3g), mean angular error by %.3g (bound %.3g)"
-          % (what, n, rel_e, bound, rel_a, bound + ANG_TOL))
-    assert rel_e <= bound
-    assert rel_a <= bound + ANG_TOL
-    ulp_mid_ok(ang, want["ang"], want["ang_plane64"], ANG_TOL, what + " angular error")
-
-
 @pytest.mark.parametrize("kind", ["normal", "nan_u", "nan_v", "inf_u", "inf_v", "neg_zero"])
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "%dx%d" % s)
 def test_flow_errors_equal_the_restatement(pdeip, shape, kind):
@@ -355,6 +263,7 @@ def test_flow_errors_host_form(pdeip):
     got = _drv().flow_errors(U, V, Ut, Vt, mask)
     assert pdeip.capi.last_error() == ""
     epe, ang, stats = run_errors(pdeip, (U, V, Ut, Vt), mask, 0)
+    check_errors((epe, ang, stats), fr.flow_errors(U, V, Ut, Vt, mask), "host form")
     assert got["epe"].tobytes() == epe.tobytes() and got["ang"].tobytes() == ang.tobytes()
     assert np.array([got["count"], got["mean_epe"], got["mean_ang"], got["max_epe"]], F64).tobytes() == stats.tobytes()
 
@@ -397,6 +306,10 @@ def test_yosemite_resident_flow_is_scored_on_the_device(pdeip, oracle):
     assert abs(stats[1] - want_all) <= 2.0 * n * 2.0 ** -53 * want_all
     assert abs(land[1] - want_land) <= 2.0 * n * 2.0 ** -53 * want_land
     assert land[1] < 0.2 and stats[1] < 0.5
+    for got, m in ((stats, None), (land, mask)):   # and in the documented order, bit for bit
+        tree = tree_of(fr.flow_errors(U, V, Ut, Vt, m))
+        assert got[0] == tree["count"] and _bits(got[1]) == _bits(tree["mean_epe"]) and _bits(got[3]) == _bits(tree["max_epe"])
+        assert abs(got[2] - tree["mean_ang"]) <= (ANG_TOL + 2.0 * (tree["ntiles"] + 18) * 2.0 ** -53) * tree["mean_ang"]
     # and its picture, with runme.m's border, against the restatement
     img, mv = dev.flow2color(gU, gV, border=10)
     ref32, rmax, ref64, valid = fr.flow2color(U, V, border=10, detail=True)
