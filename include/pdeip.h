@@ -500,7 +500,7 @@ int pdeip_ad_weights_dev(void *stream, const float *D, int nrows, int ncols, int
  * ceil(nrows/2) x ceil(ncols/2) (MATLAB's 1:2:end). */
 /* imfilter(I, G, 'replicate', 'conv') with a 5x5 kernel (:104-105); g25 = the kernel G itself, column-major (host memory) */
 int pdeip_fas_gauss5_dev(void *stream, const float *in, int nrows, int ncols, int frames, const float *g25, float *out);
-/* one pyramid step (:108-111): [1 4 6 4 1]/16 along both axes, then (1:2:end, 1:2:end, :) */
+/* one pyramid step (:108-111): [1 4 6 4 1]/16 along both axes, then (1:2:end, 1:2:end, :); out == in: PDEIP_ERR_ARG */
 int pdeip_fas_down_dev(void *stream, const float *in, int nrows, int ncols, int frames, float *out);
 /* the per-scale constants (:125-153) from the frames (0..255 range): planes = [13][frames][ncols][nrows] in the order
  * Idt, Idx, Idy, Idxx, Idyy, Idxy, Idxt, Idyt, M, Cu, Cv, Du, Dv */
@@ -517,14 +517,16 @@ int pdeip_fas_assemble_dev(void *stream, const float *planes, const float *Cu, c
 int pdeip_fas_assemble_weights_dev(void *stream, const float *planes, const float *Cu, const float *Cv, const float *U, const float *V,
                                    int nrows, int ncols, int frames, float b1, float b2, float k, float *MGd, float *CuGd, float *CvGd,
                                    float *DuGd, float *DvGd, float *wW, float *wN, float *wS, float *wE);
-/* imfilter(in*scale, [1 2 1;2 4 2;1 2 1]/16, 'replicate', 'conv')(1:2:end, 1:2:end, :) (:200, :212-217) */
+/* imfilter(in*scale, [1 2 1;2 4 2;1 2 1]/16, 'replicate', 'conv')(1:2:end, 1:2:end, :) (:200, :212-217); out == in: PDEIP_ERR_ARG */
 int pdeip_fas_restrict_dev(void *stream, const float *in, int nrows, int ncols, int frames, float scale, float *out);
-/* out = (R + A)./gd (:250-251) */
+/* out = (R + A)./gd (:250-251); elementwise, so out may be R, A or gd */
 int pdeip_fas_rhs_dev(void *stream, const float *R, const float *A, const float *gd, int nrows, int ncols, int frames, float *out);
-/* U = U + imresize((Uc-Ures)*inv_scale, size(U), 'bilinear') (:256-257); Uc, Ures are [nrows_c x ncols_c] */
+/* U = U + imresize((Uc-Ures)*inv_scale, size(U), 'bilinear') (:256-257); Uc, Ures are [nrows_c x ncols_c]; both
+ * sizes at least 2x2 (what a side of 3 halves to) */
 int pdeip_fas_prolong_add_dev(void *stream, float *U, int nrows, int ncols, const float *Uc, const float *Ures, int nrows_c,
                               int ncols_c, float inv_scale);
-/* out = imresize(in.*mul, [nrows_out ncols_out]) with imresize's default bicubic kernel, enlarging (:177-180) */
+/* out = imresize(in.*mul, [nrows_out ncols_out]) with imresize's default bicubic kernel, enlarging (:177-180); both sizes
+ * at least 2x2; out == in: PDEIP_ERR_ARG */
 int pdeip_fas_upscale_dev(void *stream, const float *in, int nrows, int ncols, float mul, int nrows_out, int ncols_out, float *out);
 /* TVdenoise8's work between two PDEsolver8 calls (matlab/denoising/TVdenoise8.m:80-86 with ADdiffWeights :119-231):
  * the anisotropic weights of Iout (double; Alvarez derivative, strongest frame per pixel, lambda = median of the

@@ -273,6 +273,7 @@ extern "C" int pdeip_fas_gauss5_dev(void *stream, const float *in, int nrows, in
 extern "C" int pdeip_fas_down_dev(void *stream, const float *in, int nrows, int ncols, int frames, float *out)
 {
     RC(check_dims("pdeip_fas_down_dev", nrows, ncols, frames));
+    if (in == out) return set_err(PDEIP_ERR_ARG, "pdeip_fas_down_dev: output aliases the input"); // every output reads 5x5 inputs
     const int nr = (nrows + 1) / 2, nc = (ncols + 1) / 2;
     hipLaunchKernelGGL(k_fas_down, pixel_grid(nr, nc, frames), dim3(256), 0, static_cast<hipStream_t>(stream), out, in, nrows, ncols, nr, nc);
     HIPCHK(hipGetLastError());
@@ -325,6 +326,7 @@ extern "C" int pdeip_fas_assemble_weights_dev(void *stream, const float *planes,
 extern "C" int pdeip_fas_restrict_dev(void *stream, const float *in, int nrows, int ncols, int frames, float scale, float *out)
 {
     RC(check_dims("pdeip_fas_restrict_dev", nrows, ncols, frames));
+    if (in == out) return set_err(PDEIP_ERR_ARG, "pdeip_fas_restrict_dev: output aliases the input"); // every output reads 3x3 inputs
     const int nr = (nrows + 1) / 2, nc = (ncols + 1) / 2;
     hipLaunchKernelGGL(k_fas_restrict, pixel_grid(nr, nc, frames), dim3(256), 0, static_cast<hipStream_t>(stream), out, in, scale, nrows, ncols,
                        nr, nc);
@@ -340,11 +342,20 @@ extern "C" int pdeip_fas_rhs_dev(void *stream, const float *R, const float *A, c
     return PDEIP_OK;
 }
 
+// The planes of the two resizing stages: the halving stages turn a side of 3 into 2, which check_dims would refuse.  The taps are
+// clamped, so a side of 2 is as good as any.
+static int check_resize_dims(const char *who, int nrows, int ncols)
+{
+    if (nrows < 2 || ncols < 2) return set_err(PDEIP_ERR_ARG, "%s: plane must be at least 2x2 (got %dx%d)", who, nrows, ncols);
+    if ((long long)nrows * ncols > 0x7fffffffLL) return set_err(PDEIP_ERR_ARG, "%s: more than 2^31-1 elements", who);
+    return PDEIP_OK;
+}
+
 extern "C" int pdeip_fas_prolong_add_dev(void *stream, float *U, int nrows, int ncols, const float *Uc, const float *Ures, int nrows_c,
                                          int ncols_c, float inv_scale)
 {
-    RC(check_dims("pdeip_fas_prolong_add_dev", nrows, ncols, 1));
-    RC(check_dims("pdeip_fas_prolong_add_dev", nrows_c, ncols_c, 1));
+    RC(check_resize_dims("pdeip_fas_prolong_add_dev", nrows, ncols));
+    RC(check_resize_dims("pdeip_fas_prolong_add_dev", nrows_c, ncols_c));
     hipLaunchKernelGGL(k_fas_prolong_add, pixel_grid(nrows, ncols, 1), dim3(256), 0, static_cast<hipStream_t>(stream), U, Uc, Ures, inv_scale,
                        nrows_c, ncols_c, nrows, ncols);
     HIPCHK(hipGetLastError());
@@ -353,9 +364,10 @@ extern "C" int pdeip_fas_prolong_add_dev(void *stream, float *U, int nrows, int 
 
 extern "C" int pdeip_fas_upscale_dev(void *stream, const float *in, int nrows, int ncols, float mul, int nrows_out, int ncols_out, float *out)
 {
-    RC(check_dims("pdeip_fas_upscale_dev", nrows, ncols, 1));
-    RC(check_dims("pdeip_fas_upscale_dev", nrows_out, ncols_out, 1));
+    RC(check_resize_dims("pdeip_fas_upscale_dev", nrows, ncols));
+    RC(check_resize_dims("pdeip_fas_upscale_dev", nrows_out, ncols_out));
     if (nrows_out < nrows || ncols_out < ncols) return set_err(PDEIP_ERR_ARG, "pdeip_fas_upscale_dev: enlarging only");
+    if (in == out) return set_err(PDEIP_ERR_ARG, "pdeip_fas_upscale_dev: output aliases the input"); // every output reads 4x4 inputs
     hipLaunchKernelGGL(k_fas_upscale, pixel_grid(nrows_out, ncols_out, 1), dim3(256), 0, static_cast<hipStream_t>(stream), out, in, mul, nrows,
                        ncols, nrows_out, ncols_out);
     HIPCHK(hipGetLastError());
