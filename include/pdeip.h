@@ -695,12 +695,14 @@ int pdeip_gac_stopping_dev(void *stream, const float *I, int nrows, int ncols, i
  * Iout = Diffusion4_v10(I_in, 'alpha', alpha, 'outer_iter', outer_iter) (matlab/diffusion/Diffusion4_v10.m) before its uint8
  * cast: the lagged-diffusivity filter as one call, resident on the device.  Iin, Iout: single [nrows x ncols x channels]; Iin is
  * never modified and Iout == Iin is allowed.  `for iter = 0:outer_iter` runs floor(outer_iter) + 1 iterations (none when
- * outer_iter < 0), each: the weights wW wN wE wS = DdiffWeights(Iout, 1e-5f) (maximum over the channels), then for every channel
+ * outer_iter < 0), each: the weights wW wN wE wS = DdiffWeights(Iout, 1e-5f) with the maximum over the channels as the .m's
+ * max(w, [], 3) takes it (a NaN of any channel is omitted, where the gateway keeps one of its first frame), then for every channel
  * a Thomas solve along every column with a = -alpha*wN, b = 2 + alpha*(wN + wS), c = -alpha*wS, one along every row with
  * a = -alpha*wW, b = 2 + alpha*(wW + wE), c = -alpha*wE, both with d = Iout(:,:,k), and Iout(:,:,k) = ver + hor; every operation
  * in single, alpha rounded to single, in the order of the .m.  A NaN member (or prm == NULL) keeps the driver's default (alpha
  * 25, outer_iter 5).  Refused with PDEIP_ERR_ARG before any HIP call: nrows or ncols < 2, channels < 1, a non-finite alpha, an
- * infinite outer_iter.  pdeip_set_mode does not apply (a Thomas solve has one order). */
+ * infinite outer_iter; with PDEIP_ERR_UNSUPPORTED: more than 65535 columns or channels.  pdeip_set_mode does not apply (a Thomas
+ * solve has one order). */
 typedef struct pdeip_diffusion4_params {
     double alpha, outer_iter;
 } pdeip_diffusion4_params;

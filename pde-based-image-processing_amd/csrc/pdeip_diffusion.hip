@@ -3,6 +3,8 @@
 //
 // Kernels: csrc/pdeip_diffusion.hpp.  The weights are k_diffweights6 (csrc/pdeip_pointwise.hpp, DdiffWeights) launched here
 // directly: its entry point pdeip_diffweights6_dev keeps the gateway's 3x3 minimum, and this driver accepts 2-element lines.
+// The maximum over the channels is the .m's max(w, [], 3), which omits a NaN of any channel (k_diffweights6<true>); the
+// gateway's C keeps a NaN of its first frame (<false>, pdeip_diffweights6_dev).
 // A Thomas solve has one order, so pdeip_set_mode does not apply.
 //
 // Build (build.py): hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -c, one object per translation unit.
@@ -20,11 +22,17 @@ namespace {
 // Everything refused is refused here, before any HIP call.  NaN members (or no struct) keep the driver's defaults, alpha 25 and
 // outer_iter 5 (Diffusion4_v10.m:36-37).  `for iter = 0:outer_iter` (:44) runs floor(outer_iter) + 1 iterations when
 // outer_iter >= 0 and none below.  MATLAB's TDMA indexes d(0) on a line shorter than 2, so such images are refused.
+// The column is blockIdx.y of k_diffweights6 and the channel blockIdx.y of k_diff4_lines: more than MAX_GRID_Y of either is
+// the launch geometry's refusal (PDEIP_ERR_UNSUPPORTED), not the contract's.
+constexpr int MAX_GRID_Y = 65535;
+
 int diff4_args(const char *who, int nrows, int ncols, int channels, const pdeip_diffusion4_params *u, float *alpha, int *iters)
 {
     if (nrows < 2 || ncols < 2)
         return set_err(PDEIP_ERR_ARG, "%s: image must be at least 2x2 (got %dx%d)", who, nrows, ncols);
     if (channels < 1) return set_err(PDEIP_ERR_ARG, "%s: number of channels must be >= 1 (got %d)", who, channels);
+    if (ncols > MAX_GRID_Y) return set_err(PDEIP_ERR_UNSUPPORTED, "%s: more than %d columns (got %d)", who, MAX_GRID_Y, ncols);
+    if (channels > MAX_GRID_Y) return set_err(PDEIP_ERR_UNSUPPORTED, "%s: more than %d channels (got %d)", who, MAX_GRID_Y, channels);
     if ((long long)nrows * ncols * channels > 0x7fffffffLL) return set_err(PDEIP_ERR_ARG, "%s: more than 2^31-1 elements", who);
     double a = 25.0, k = 5.0;
     if (u) {
@@ -41,9 +49,9 @@ int diff4_args(const char *who, int nrows, int ncols, int channels, const pdeip_
 
 } // namespace
 
-// The run: Iout = single(I_in), then per outer iteration the weights of Iout (maximum over the channels), the column and row
-// solves of every channel, Iout = ver + hor.  Workspace (WS_DRIVER): the four [nrows x ncols] weight planes (k_diffweights6
-// writes frame 0 only), then xc, xr and the column and row cp/dp, [nrows x ncols x channels] each.
+// The run: Iout = single(I_in), then per outer iteration the weights of Iout (maximum over the channels, NaN omitted), the
+// column and row solves of every channel, Iout = ver + hor.  Workspace (WS_DRIVER): the four [nrows x ncols] weight planes
+// (k_diffweights6 writes frame 0 only), then xc, xr and the column and row cp/dp, [nrows x ncols x channels] each.
 extern "C" int pdeip_diffusion4_dev(void *stream, const float *Iin, int nrows, int ncols, int channels,
                                     const pdeip_diffusion4_params *prm, float *Iout)
 {
@@ -67,7 +75,7 @@ extern "C" int pdeip_diffusion4_dev(void *stream, const float *Iin, int nrows, i
         const int rb = (nrows + D4_BLOCK - 1) / D4_BLOCK, cb = (ncols + D4_BLOCK - 1) / D4_BLOCK;
         const dim3 lines((unsigned)(rb + cb), (unsigned)channels), sum((unsigned)((nc + 255) / 256));
         for (int it = 0; it < iters; it++) {
-            hipLaunchKernelGGL(k_diffweights6, pixel_grid(nrows, ncols, 1), dim3(256), 0, s, wW, wN, wE, wS, Iout, nrows, ncols,
+            hipLaunchKernelGGL(k_diffweights6<true>, pixel_grid(nrows, ncols, 1), dim3(256), 0, s, wW, wN, wE, wS, Iout, nrows, ncols,
                                channels, 0.00001f);
             hipLaunchKernelGGL(k_diff4_lines, lines, dim3(D4_BLOCK), 0, s, Iout, wW, wN, wE, wS, xc, xr, cpc, dpc, cpr, dpr, nrows,
                                ncols, rb, alpha);

@@ -1,6 +1,7 @@
 // pdeip_diffusion.hpp -- the nonlinear (lagged-diffusivity) diffusion filter matlab/diffusion/Diffusion4_v10.m: the line solves
 // of one outer iteration and the combine that ends it.  The weights are the DdiffWeights kernel (k_diffweights6,
-// csrc/pdeip_pointwise.hpp) with eps = 0.00001f and the channels as its frames.
+// csrc/pdeip_pointwise.hpp) with eps = 0.00001f and the channels as its frames, in its <true> form: the maximum over the channels
+// omits a NaN of any channel, as the .m's max(w, [], 3).
 //
 // One outer iteration (Diffusion4_v10.m:44-62), every channel k of Iout solved independently with the iteration's weights:
 //   ver = TDMA(-alpha*wN, 2 + alpha*(wN + wS), -alpha*wS, Iout(:,:,k))     along every column

@@ -177,6 +177,19 @@ __device__ __forceinline__ float dw_inv_sqrt(float t, float eps)
     return 1.0f / sqrtf(s);
 }
 
+// The maximum over the frames, folded into m frame by frame.  The gateway's rule (OMIT_NAN = false, Calc_wW :143 and its
+// siblings): frame 0 initialises, a later frame replaces it when t > m, so that a NaN of frame 0 stays and a NaN of a later
+// frame is dropped.  MATLAB's max(w, [], 3) of Diffusion4_v10.m's DiffWeights (OMIT_NAN = true) omits a NaN of any frame: a NaN
+// m is replaced by whatever comes, and the result is NaN only where every frame's term is.  Comparisons only, no fmaxf; the
+// terms are sums of squares, so -0 does not arise and ties have equal bits.
+template <bool OMIT_NAN>
+__device__ __forceinline__ void dw_fold(float &m, float t, int k)
+{
+    if (k == 0) m = t;
+    else if (t > m || (OMIT_NAN && m != m)) m = t;
+}
+
+template <bool OMIT_NAN>
 static __global__ void k_diffweights6(float *wW, float *wN, float *wE, float *wS, const float *D,
                                int nrows, int ncols, int nframes, float eps)
 {
@@ -192,25 +205,25 @@ static __global__ void k_diffweights6(float *wW, float *wN, float *wE, float *wS
             A = dc - d[pos - nrows];
             B = vc + dw_ver(d, i, j - 1, nrows);
             A = A * A; B = B * B; t = A + B;
-            if (k == 0) tW = t; else if (t > tW) tW = t;
+            dw_fold<OMIT_NAN>(tW, t, k);
         }
         if (i >= 1) { // Calc_wN :177-200
             A = dc - d[pos - 1];
             B = hc + dw_hor(d, i - 1, j, nrows, ncols);
             A = A * A; B = B * B; t = A + B;
-            if (k == 0) tN = t; else if (t > tN) tN = t;
+            dw_fold<OMIT_NAN>(tN, t, k);
         }
         if (j <= ncols - 2) { // Calc_wE :236-258
             A = dc - d[pos + nrows];
             B = vc + dw_ver(d, i, j + 1, nrows);
             A = A * A; B = B * B; t = A + B;
-            if (k == 0) tE = t; else if (t > tE) tE = t;
+            dw_fold<OMIT_NAN>(tE, t, k);
         }
         if (i <= nrows - 2) { // Calc_wS :289-311
             A = dc - d[pos + 1];
             B = hc + dw_hor(d, i + 1, j, nrows, ncols);
             A = A * A; B = B * B; t = A + B;
-            if (k == 0) tS = t; else if (t > tS) tS = t;
+            dw_fold<OMIT_NAN>(tS, t, k);
         }
     }
     // cells the reference never writes keep the gateway's zero initialisation

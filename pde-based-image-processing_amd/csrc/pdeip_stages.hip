@@ -71,7 +71,8 @@ extern "C" int pdeip_diffweights6_dev(void *stream, const float *D, int nrows, i
                                       float eps, float *wW, float *wN, float *wE, float *wS)
 {
     RC(check_dims("pdeip_diffweights6_dev", nrows, ncols, nframes));
-    hipLaunchKernelGGL(k_diffweights6, pixel_grid(nrows, ncols, 1), dim3(256), 0, static_cast<hipStream_t>(stream),
+    // the gateway's maximum over the frames: a NaN of frame 0 stays, a NaN of a later frame is dropped
+    hipLaunchKernelGGL(k_diffweights6<false>, pixel_grid(nrows, ncols, 1), dim3(256), 0, static_cast<hipStream_t>(stream),
                        wW, wN, wE, wS, D, nrows, ncols, nframes, eps);
     HIPCHK(hipGetLastError());
     return PDEIP_OK;

@@ -22,8 +22,11 @@ def _shift(A, di, dj):
     return np.roll(np.roll(A, di, axis=0), dj, axis=1)
 
 
-def diff_weights(D, dtype=np.float32):
-    """[wW wN wE wS] = DiffWeights(D) (:97-127) as [rows, cols] planes."""
+def diff_weights(D, dtype=np.float32, channel_max=None, eps=0.00001):
+    """[wW wN wE wS] = DiffWeights(D) (:97-127) as [rows, cols] planes.  `channel_max` (the .m's max(w, [], 3) = np.fmax.reduce when
+    None) and `eps` (the .m's 0.00001) are open only so that tests/diffusion_nan_cases.py can state the C gateway's rule next to the
+    .m's with the same arithmetic around it."""
+    channel_max = channel_max or (lambda T: np.fmax.reduce(T, axis=2))  # max(w, [], 3): NaN omitted, as MATLAB's max
     t = np.dtype(dtype).type
     D = np.asarray(D, dtype)
     if D.ndim == 2:
@@ -37,8 +40,8 @@ def diff_weights(D, dtype=np.float32):
         def w(di, dj, Dd):
             A = _shift(D, di, dj) - D
             B = Dd + _shift(Dd, di, dj)
-            m = np.fmax.reduce(A * A + B * B, axis=2)  # max(w, [], 3): NaN omitted, as MATLAB's max
-            return (t(1) / np.sqrt(m + t(0.00001))).astype(dtype)
+            m = channel_max(A * A + B * B)
+            return (t(1) / np.sqrt(m + t(eps))).astype(dtype)
 
         wW, wE = w(0, 1, Dver), w(0, -1, Dver)
         wN, wS = w(1, 0, Dhor), w(-1, 0, Dhor)
@@ -71,12 +74,12 @@ def tdma(a, b, c, d):
     return x
 
 
-def outer_iteration(I, alpha, dtype=np.float32):
+def outer_iteration(I, alpha, dtype=np.float32, channel_max=None):
     """One pass of the loop body (:46-61) on I [rows, cols, C]; returns the new Iout."""
     t = np.dtype(dtype).type
     I = np.asarray(I, dtype)
     al = t(alpha)
-    wW, wN, wE, wS = diff_weights(I, dtype)
+    wW, wN, wE, wS = diff_weights(I, dtype, channel_max)
     with np.errstate(all="ignore"):
         a_ver, b_ver, c_ver = (-al) * wN, t(2) + al * (wN + wS), (-al) * wS
         a_hor, b_hor, c_hor = ((-al) * wW).T, (t(2) + al * (wW + wE)).T, ((-al) * wE).T
@@ -93,14 +96,14 @@ def iterations(outer_iter):
     return int(math.floor(outer_iter)) + 1 if outer_iter >= 0 else 0
 
 
-def Diffusion4_v10(I_in, alpha=25, outer_iter=5, dtype=np.float32):
+def Diffusion4_v10(I_in, alpha=25, outer_iter=5, dtype=np.float32, channel_max=None):
     """Iout of Diffusion4_v10(I_in, 'alpha', alpha, 'outer_iter', outer_iter) before uint8 (:41-62), in I_in's shape."""
     I = np.asarray(I_in, dtype=np.float32).astype(dtype)
     shape = I.shape
     if I.ndim == 2:
         I = I[:, :, None]
     for _ in range(iterations(outer_iter)):
-        I = outer_iteration(I, alpha, dtype)
+        I = outer_iteration(I, alpha, dtype, channel_max)
     return np.asfortranarray(I.reshape(shape))
 
 

@@ -433,7 +433,9 @@ def diff_laced(value):
 @functools.lru_cache(maxsize=None)
 def diff_one_pixel(value):
     """NaN or +Inf on ONE pixel of ONE channel: with outer_iter = 0 (one iteration) the weights stay finite -- max(., [], 3) drops
-    the NaN, and 1/sqrt(Inf) is 0 -- so that only the two lines through the pixel carry it."""
+    the NaN, and 1/sqrt(Inf) is 0 -- so that only the two lines through the pixel carry it.  The pixel is in channel 1, the one
+    place where the .m's maximum and the DdiffWeights gateway's (which keeps a NaN of frame 0) agree; diffusion_nan_cases.py has the
+    pixel in every channel."""
     I = diff_image(303, DIFF_SHAPE)
     I[DIFF_PIXEL] = F32(value)
     return _ro(I)

@@ -216,7 +216,10 @@ def _prm(pdeip, alpha, outer_iter):
 
 REFUSED = [((1, 5, 1), (25.0, 5.0), "at least 2x2"), ((5, 1, 3), (25.0, 5.0), "at least 2x2"), ((1, 1, 1), (25.0, 5.0), "at least 2x2"),
            ((4, 4, 0), (25.0, 5.0), "channels"), ((4, 4, 1), (np.inf, 5.0), "alpha"), ((4, 4, 1), (-np.inf, 5.0), "alpha"),
-           ((4, 4, 1), (1e39, 5.0), "alpha"), ((4, 4, 3), (25.0, np.inf), "outer_iter"), ((4, 4, 3), (25.0, -np.inf), "outer_iter")]
+           ((4, 4, 1), (1e39, 5.0), "alpha"), ((4, 4, 3), (25.0, np.inf), "outer_iter"), ((4, 4, 3), (25.0, -np.inf), "outer_iter"),
+           ((2, 65536, 1), (25.0, 5.0), "more than 65535 columns"), ((2, 2, 65536), (25.0, 5.0), "more than 65535 channels")]
+# the column is blockIdx.y of the weight kernel and the channel blockIdx.y of the line kernel: the launch geometry's refusals
+UNSUPPORTED = ("more than 65535 columns", "more than 65535 channels")
 
 
 @pytest.mark.parametrize("shape,params,msg", REFUSED)
@@ -226,10 +229,11 @@ def test_c_abi_refuses_without_a_gpu(pdeip, shape, params, msg):
     z = np.zeros(max(1, shape[0] * shape[1] * max(shape[2], 1)), F32)
     o = np.zeros_like(z)
     prm = _prm(pdeip, *params)
+    code = capi.PDEIP_ERR_UNSUPPORTED if msg in UNSUPPORTED else capi.PDEIP_ERR_ARG
     rc = lib.pdeip_diffusion4(z.ctypes.data, shape[0], shape[1], shape[2], ctypes.addressof(prm), o.ctypes.data)
-    assert rc == capi.PDEIP_ERR_ARG and msg in capi.last_error(), capi.last_error()
+    assert rc == code and msg in capi.last_error(), capi.last_error()
     rc = lib.pdeip_diffusion4_dev(None, z.ctypes.data, shape[0], shape[1], shape[2], ctypes.addressof(prm), o.ctypes.data)
-    assert rc == capi.PDEIP_ERR_ARG and msg in capi.last_error(), capi.last_error()
+    assert rc == code and msg in capi.last_error(), capi.last_error()
 
 
 def test_c_abi_refuses_null_pointers(pdeip):
