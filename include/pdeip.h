@@ -1243,6 +1243,96 @@ int pdeip_flow_interpolate(const float *I0, const float *I1, int channels, const
                            const float *Vb, int nrows, int ncols, double t, const pdeip_interp_params *prm, float *It_out,
                            float *Ut_out, float *Vt_out, float *source_out);
 
+/* ---- structure-tensor anisotropic diffusion (csrc/pdeip_stensor.hip) --------------------------------------------------------
+ * Weickert's edge-enhancing (EED) and coherence-enhancing (CED) diffusion, each semi-implicit step (I - tau A(u^k)) u^{k+1} = u^k
+ * one PDEsolver8 solve by pdeip_pde_sor8_dev / pdeip_pde_alr8_dev.  Not in the reference toolbox; tests/stensor_ref.py restates
+ * every stage.  Planes are single, column-major [nrows x ncols x frames]; x runs along the columns, y down the rows.
+ *
+ * pdeip_gauss_taps (host only, no HIP call): R = ceil(3 sigma) and the 2R + 1 taps g[k] = exp(-k^2 / (2 sigma^2)), k = -R..R, in
+ * double, divided by their double sum (added in ascending k), each rounded to single; sigma = 0: R = 0 and the tap 1.
+ * PDEIP_ERR_ARG: sigma NaN, negative or infinite, capacity < 2R + 1 (nothing written); PDEIP_ERR_UNSUPPORTED: R > 32.
+ *
+ * pdeip_gauss / pdeip_gauss_dev: out = G_sigma * in, separable, border 'replicate'.  Pass 1 runs along the rows (down a column)
+ * and its result is rounded to single; pass 2 runs along the columns.  Each output of a pass is
+ * ((g[-R] x[-R] + g[-R+1] x[-R+1]) + ...) + g[R] x[R] in single, left to right, no FMA, indices clamped to the frame.
+ * sigma = 0 is a copy (1 launch), otherwise 2 launches; the intermediate plane is library workspace.  Refused before any HIP
+ * call: what pdeip_gauss_taps refuses, a NULL pointer, a frame below 3x3, frames < 1, more than 2^31-1 elements, out == in
+ * (PDEIP_ERR_ARG); more than 65535 columns or frames (PDEIP_ERR_UNSUPPORTED).
+ *
+ * pdeip_structure_tensor_dev: J = [J11, J12, J22], three planes [nrows x ncols], of I [nrows x ncols x channels]:
+ *   v   = G_sigma * I per channel (pdeip_gauss_dev; sigma = 0: I itself)
+ *   gx, gy  the Alvarez 3x3 derivative of v toward increasing column / row, border 'replicate', single: with w1 = 1/(4 + sqrt 8) and
+ *       w2 = sqrt 2/(4 + sqrt 8) rounded to single, d-, d0, d+ the differences v(., j+1) - v(., j-1) on rows i-1, i, i+1 (for gy:
+ *       v(i+1, .) - v(i-1, .) on columns j-1, j, j+1), the derivative is (w1 d- + w2 d0) + w1 d+
+ *   J11 = sum_c gx^2, J12 = sum_c gx gy, J22 = sum_c gy^2, single, channel 0's product first and the others added in index order
+ *       (Weickert's joint tensor of a colour image)
+ *   J   = G_rho * J as three frames (rho = 0: the products themselves)
+ * 2 [sigma > 0] + 1 + 2 [rho > 0] launches.  Refused as pdeip_gauss_dev refuses, for both scales; J == I.
+ *
+ * pdeip_st_weights_dev: the diffusion tensor and the eight weights, w8 = eight planes [nrows x ncols] in the order W NW N NE E
+ * SE S SW.  Per pixel, in double from the single J:
+ *   s = j11 + j22, d = j11 - j22, r = sqrt(d d + 4 j12 j12), mu1 = 0.5 (s + r), c2 = r > 0 ? d / r : 1, s2 = r > 0 ? 2 j12 / r : 0
+ *   EED (mode 0): l1 = mu1 > 0 ? 1 - exp(-3.31488 / q^4) : 1 with q = mu1 / (lambda lambda), q^4 = (q q)(q q); l2 = 1
+ *   CED (mode 1): l1 = alpha; l2 = r > 0 ? alpha + (1 - alpha) exp(-C / (r r)) : alpha
+ *   m = 0.5 (l1 + l2), h = 0.5 (l1 - l2), D11 = m + h c2, D22 = m - h c2, D12 = h s2
+ *   the eight weights by TVdenoise8's assembly with dyy := D11, dxx := D22, dxy := D12 (wW = (D11 + D11 of the west pixel) / 2, wN =
+ *   (D22 + D22 north) / 2, wNW = (D12 + D12 north-west) / 4, wNE = -(D12 + D12 north-east) / 4, and so on), a weight across the
+ *   frame's edge zero; sum = ((wW + wNW) + wN) + ... + wSW; w8[k] = (float)(tau w_k), TRACE = (float)(1 + tau sum).
+ * A NaN in J fails every comparison above (a flat pixel's tensor).  Only mode, lambda, alpha and C of `prm` are read (NaN or
+ * prm == NULL: the defaults below); tau is the argument.  1 launch.  Refused before any HIP call: a NULL plane, a frame below 3x3,
+ * more than 65535 columns, an unknown mode, lambda <= 0 or not finite (EED), alpha outside [0, 1], C <= 0 or not finite (CED), tau
+ * NaN, negative or infinite.
+ *
+ *
+ * The ring.  PDEsolver8 relaxes the interior of a plane and after every sweep copies the neighbours into the plane's outer ring
+ * of pixels (pdeSolvers.c:249-262).  Handed the image as it is, it would never relax the image's edge pixels, and the copies make
+ * the structure tensor there degenerate: on the scene of tests/test_stensor_ref.py ten such iterations leave an RMS error of 66
+ * on the first row and of 17 overall, against 7.9 when every pixel is relaxed.  So a step solves on planes [(nrows + 2) x
+ * (ncols + 2)] that hold the image inside a ring of one pixel: every pixel of the image is an interior pixel of the solve; its
+ * weights across the image's edge are zero (no flux, the system symmetric with unit row sums); the ring is the solver's.
+ *   pdeip_st_weights_padded_dev  pdeip_st_weights_dev onto such planes: TRACE [(nrows+2) x (ncols+2)] and w8, eight of them, hold
+ *                                the image's values inside and TRACE = 1, weights 0 on the ring.  1 launch.
+ *   pdeip_st_pad_dev             out (and out2 unless NULL) [(nrows+2) x (ncols+2) x frames] = in [nrows x ncols x frames] inside a
+ *                                ring of its nearest pixels.  1 launch; out == in refused.
+ *   pdeip_st_crop_dev            out [nrows x ncols x frames] = the inside of in.  1 launch; out == in refused.
+ * These refuse what pdeip_st_weights_dev / pdeip_gauss_dev refuse for the frame, and more than 65533 columns.
+ *
+ * pdeip_diffusion8 / pdeip_diffusion8_dev: Iout = the filtered Iin, both [nrows x ncols x channels], 0..255 data as Diffusion4_v10
+ * takes it; Iout == Iin is allowed, otherwise Iin is untouched.  Iout = Iin, then `iters` times: J of Iout; the weights and
+ * TRACE (padded); X = B = Iout inside its ring (pdeip_st_pad_dev, all channels at once); per channel one call of
+ * pdeip_pde_sor8_dev (solver 1, inner_iter sweeps at omega) or pdeip_pde_alr8_dev (solver 2: one iteration whatever inner_iter
+ * says, like the reference) in place on the channel's X, nframes = 1, in the library's current ordering (pdeip_set_mode), every
+ * channel on the one set of weight planes; Iout = the inside of X (pdeip_st_crop_dev).
+ * Every member is a double; NaN (or prm == NULL) takes the default:
+ *   mode 1 (CED): sigma 0.7, rho 4, alpha 0.001, C 1;  mode 0 (EED): sigma 1.5, rho 0, lambda 6;
+ *   both: tau 1, iters 10, solver 1, inner_iter 4, omega 1.  Counts are floored; a negative count is none.
+ * At tau = 1 every row of the system stays weakly diagonally dominant; at tau = 2 it does not.
+ * _dev: one stream, nothing read back, no allocation once an eager call has created the workspaces: graph-capturable.  Launches
+ * (pdeip_last_launch_count()), a function of shape and parameters alone:
+ *   [Iout != Iin] + iters * (2 [sigma > 0] + 1 + 2 [rho > 0] + 3 + channels * L)
+ * with L what pdeip_last_launch_count() reports after the solver call on one [(nrows+2) x (ncols+2)] plane in the current ordering.
+ * Refused before any HIP call: a NULL pointer; a frame below 3x3, channels < 1, more than 2^31-1 elements; sigma, rho or tau NaN,
+ * negative or infinite; what pdeip_st_weights_dev refuses; omega not finite in single; an infinite or over-large iters or
+ * inner_iter; a workspace (3 planes of the image, 9 + 2 channels planes with the ring) of more than 2^31-1 elements
+ * (PDEIP_ERR_ARG); a solver other than 1 or 2 (PDEIP_ERR_SOLVER); a radius above 32, more than 65533 columns or 65535 channels
+ * (PDEIP_ERR_UNSUPPORTED). */
+typedef struct pdeip_diffusion8_params {
+    double mode, sigma, rho, lambda, alpha, C, tau, iters, inner_iter, omega, solver;
+} pdeip_diffusion8_params;
+int pdeip_gauss_taps(double sigma, float *taps, int capacity, int *radius);
+int pdeip_gauss(const float *in, int nrows, int ncols, int frames, double sigma, float *out);
+int pdeip_gauss_dev(void *stream, const float *in, int nrows, int ncols, int frames, double sigma, float *out);
+int pdeip_structure_tensor_dev(void *stream, const float *I, int nrows, int ncols, int channels, double sigma, double rho, float *J);
+int pdeip_st_weights_dev(void *stream, const float *J, int nrows, int ncols, const pdeip_diffusion8_params *prm, double tau,
+                         float *TRACE, float *w8);
+int pdeip_st_weights_padded_dev(void *stream, const float *J, int nrows, int ncols, const pdeip_diffusion8_params *prm, double tau,
+                                float *TRACE, float *w8);
+int pdeip_st_pad_dev(void *stream, const float *in, int nrows, int ncols, int frames, float *out, float *out2);
+int pdeip_st_crop_dev(void *stream, const float *in, int nrows, int ncols, int frames, float *out);
+int pdeip_diffusion8(const float *Iin, int nrows, int ncols, int channels, const pdeip_diffusion8_params *prm, float *Iout);
+int pdeip_diffusion8_dev(void *stream, const float *Iin, int nrows, int ncols, int channels, const pdeip_diffusion8_params *prm,
+                         float *Iout);
+
 #ifdef __cplusplus
 }
 #endif

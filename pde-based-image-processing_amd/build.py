@@ -24,7 +24,7 @@ UNITS = {
     "pdeip_sor9.hip": ["pdeip_models.hpp", "pdeip_pointwise.hpp", "pdeip_sor_pde8.hpp", "pdeip_sor_pde8_persist.hpp", "pdeip_sor_exact.hpp", "pdeip_sor_rb.hpp", "pdeip_persist_host.hpp", "pdeip_sor_small.hpp", "pdeip_sor_plan.hpp"],
     "pdeip_line.hip": ["pdeip_alr.hpp", "pdeip_alr_plan.hpp", "pdeip_models.hpp"],
     "pdeip_stages.hip": ["pdeip_models.hpp", "pdeip_pointwise.hpp", "pdeip_flow.hpp", "pdeip_cswap.hpp", "pdeip_fas.hpp", "pdeip_sym.hpp", "pdeip_sym_warp.hpp", "pdeip_pyr.hpp",
-                         "pdeip_tv.hpp"],
+                         "pdeip_tv.hpp", "pdeip_tensor8.hpp"],
     "pdeip_host.hip": [],
     "pdeip_drivers.hip": [],
     "pdeip_multi.hip": [],
@@ -38,6 +38,7 @@ UNITS = {
     "pdeip_crosscheck.hip": ["pdeip_crosscheck.hpp", "pdeip_sym_warp.hpp", "pdeip_reduce.hpp", "pdeip_bilinear.hpp"],
     "pdeip_inpaint.hip": ["pdeip_inpaint.hpp", "pdeip_pyr.hpp", "pdeip_pointwise.hpp"],
     "pdeip_interp.hip": ["pdeip_interp.hpp", "pdeip_bilinear.hpp"],
+    "pdeip_stensor.hip": ["pdeip_stensor.hpp", "pdeip_tensor8.hpp", "pdeip_models.hpp", "pdeip_pointwise.hpp"],
 }
 # -ffp-contract=off is part of the parity contract (the reference is FMA-free C).
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]

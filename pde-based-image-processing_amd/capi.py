@@ -193,6 +193,17 @@ SIGNATURES = {
     "pdeip_interp_blend_dev": [_P, _P, _P, _I, _P, _P, _P, _P, _I, _I, ctypes.c_double, _P, _P],
     "pdeip_flow_interpolate_dev": [_P, _P, _P, _I, _P, _P, _P, _P, _I, _I, ctypes.c_double, _P, _P, _P, _P, _P],
     "pdeip_flow_interpolate": [_P, _P, _I, _P, _P, _P, _P, _I, _I, ctypes.c_double, _P, _P, _P, _P, _P],
+    # structure-tensor anisotropic diffusion (csrc/pdeip_stensor.hip)
+    "pdeip_gauss_taps": [ctypes.c_double, _P, _I, ctypes.POINTER(ctypes.c_int)],
+    "pdeip_gauss": [_P, _I, _I, _I, ctypes.c_double, _P],
+    "pdeip_gauss_dev": [_P, _P, _I, _I, _I, ctypes.c_double, _P],
+    "pdeip_structure_tensor_dev": [_P, _P, _I, _I, _I, ctypes.c_double, ctypes.c_double, _P],
+    "pdeip_st_weights_dev": [_P, _P, _I, _I, _P, ctypes.c_double, _P, _P],
+    "pdeip_st_weights_padded_dev": [_P, _P, _I, _I, _P, ctypes.c_double, _P, _P],
+    "pdeip_st_pad_dev": [_P, _P, _I, _I, _I, _P, _P],
+    "pdeip_st_crop_dev": [_P, _P, _I, _I, _I, _P],
+    "pdeip_diffusion8": [_P, _I, _I, _I, _P, _P],
+    "pdeip_diffusion8_dev": [_P, _P, _I, _I, _I, _P, _P],
     # library state
     "pdeip_set_mode": [_I],
     "pdeip_get_mode": [],

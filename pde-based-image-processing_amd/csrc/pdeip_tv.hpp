@@ -14,6 +14,7 @@
 
 #include "pdeip_models.hpp"
 #include "pdeip_pointwise.hpp"
+#include "pdeip_tensor8.hpp"
 
 namespace pdeip {
 
@@ -185,12 +186,8 @@ __global__ void __launch_bounds__(256) k_tvsel_scan(TvSelectState *st, double *l
 // The eight weights (times alpha, as single), TRACE and B of one outer iteration (TVdenoise8.m:82-86).
 // Tile form of the tensor stencils below: a workgroup of 64 x 4 threads owns 64 rows x 4 columns and evaluates the diffusion
 // tensor (one double division per pixel) ONCE for its 66 x 6 neighbourhood into LDS -- circshift wrap-around at the frame
-// edges as the drivers have it -- instead of nine times per output pixel.  Same expressions, same bits.
-constexpr int TT_R = 64, TT_C = 4;
-struct TensorTile {
-    double dyy[TT_C + 2][TT_R + 2], dxx[TT_C + 2][TT_R + 2], dxy[TT_C + 2][TT_R + 2];
-};
-
+// edges as the drivers have it -- instead of nine times per output pixel.  Same expressions, same bits.  The tile and the
+// assembly of the eight weights from it are pdeip_tensor8.hpp's.
 __device__ __forceinline__ void tensor_tile_fill(TensorTile &T, const double *gx, const double *gy, const double *nrm, double lambda, int i0,
                                                  int j0, int nrows, int ncols)
 {
@@ -223,27 +220,12 @@ k_tv_assemble(float *TRACE, float *B, float *aW, float *aNW, float *aN, float *a
     const int i = i0 + threadIdx.x, j = j0 + threadIdx.y;
     if (i >= nrows || j >= ncols) return;
     const size_t n = (size_t)nrows * ncols, pos = (size_t)j * nrows + i;
-    const int r = threadIdx.x + 1, c = threadIdx.y + 1;
-    const double dyy = T.dyy[c][r], dxx = T.dxx[c][r], dxy = T.dxy[c][r];
-    const bool c0 = j == 0, cE = j == ncols - 1, r0 = i == 0, rE = i == nrows - 1;
-    const double W = c0 ? 0.0 : 0.5 * (dyy + T.dyy[c - 1][r]);
-    const double NW = (c0 || r0) ? 0.0 : 0.25 * (dxy + T.dxy[c - 1][r - 1]);
-    const double N = r0 ? 0.0 : 0.5 * (dxx + T.dxx[c][r - 1]);
-    const double NE = (cE || r0) ? 0.0 : -0.25 * (dxy + T.dxy[c + 1][r - 1]);
-    const double E = cE ? 0.0 : 0.5 * (dyy + T.dyy[c + 1][r]);
-    const double SE = (cE || rE) ? 0.0 : 0.25 * (dxy + T.dxy[c + 1][r + 1]);
-    const double S = rE ? 0.0 : 0.5 * (dxx + T.dxx[c][r + 1]);
-    const double SW = (rE || c0) ? 0.0 : -0.25 * (dxy + T.dxy[c - 1][r + 1]);
-    double sum = W + NW; // wW+wNW+wN+wNE+wE+wSE+wS+wSW, left to right
-    sum = sum + N;
-    sum = sum + NE;
-    sum = sum + E;
-    sum = sum + SE;
-    sum = sum + S;
-    sum = sum + SW;
+    double w[8];
+    const double sum = tensor_weights8(T, threadIdx.y + 1, threadIdx.x + 1, j == 0, j == ncols - 1, i == 0, i == nrows - 1, w);
     const float asum = (float)(alpha * sum);
-    const float w8[8] = {(float)(alpha * W), (float)(alpha * NW), (float)(alpha * N), (float)(alpha * NE),
-                         (float)(alpha * E), (float)(alpha * SE), (float)(alpha * S), (float)(alpha * SW)};
+    float w8[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) w8[k] = (float)(alpha * w[k]);
     float *outs[8] = {aW, aNW, aN, aNE, aE, aSE, aS, aSW};
     for (int f = 0; f < nframes; ++f) { // the weights are repmat'ed over the frames (:222-231); PsiData is per frame
         const size_t p = (size_t)f * n + pos;

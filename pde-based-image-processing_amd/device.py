@@ -294,6 +294,109 @@ def diffusion4(I, alpha, outer_iter, out):
     capi.call("pdeip_diffusion4_dev", _stream(), I.data_ptr(), nrows, ncols, C, ctypes.addressof(prm), out.data_ptr())
 
 
+# ---- structure-tensor anisotropic diffusion (csrc/pdeip_stensor.hip) ---------------------------------------
+
+class Diffusion8Params(ctypes.Structure):
+    """pdeip_diffusion8_params: every member a double, NaN keeps the default of the mode (include/pdeip.h)."""
+    _fields_ = [(k, ctypes.c_double) for k in ("mode", "sigma", "rho", "lambda_", "alpha", "C", "tau", "iters", "inner_iter", "omega", "solver")]
+
+
+_D8_KEYS = {k: k for k, _ in Diffusion8Params._fields_ if k not in ("mode", "lambda_")}
+_D8_KEYS.update({"lambda": "lambda_", "lambda_": "lambda_"})
+_D8_MODES = {"eed": 0.0, "ced": 1.0}
+
+
+def diffusion8_params(mode="ced", who="diffusion8", **param):
+    """The parameter struct of a mode ('eed' | 'ced') with the named members set (lambda: pass **{"lambda": v} or lambda_=v)."""
+    if mode not in _D8_MODES:
+        raise ValueError("%s: mode must be 'eed' or 'ced' (got %r)" % (who, mode))
+    prm = Diffusion8Params(*([float("nan")] * len(Diffusion8Params._fields_)))
+    prm.mode = _D8_MODES[mode]
+    for k, v in param.items():
+        if k not in _D8_KEYS:
+            raise TypeError("%s: unknown parameter %r" % (who, k))
+        setattr(prm, _D8_KEYS[k], float(v))
+    return prm
+
+
+def gauss_taps(sigma):
+    """(taps as a float32 numpy array of 2R + 1, R) of pdeip_gauss_taps: host only."""
+    buf = (ctypes.c_float * 65)()
+    R = ctypes.c_int(-1)
+    capi.call("pdeip_gauss_taps", float(sigma), ctypes.addressof(buf), 65, ctypes.byref(R))
+    return np.array(buf[:2 * R.value + 1], dtype=np.float32), R.value
+
+
+def gaussian(I, sigma, out=None):
+    """out = G_sigma * I, separable, 'replicate' border, per plane of I [(F,) ncols, nrows]; out must not be I."""
+    _chk(I)
+    out = torch.empty_like(I) if out is None else out
+    _chk(out)
+    if out.shape != I.shape:
+        raise capi.PdeipError(capi.PDEIP_ERR_ARG, "gaussian: out is %s but I is %s" % (tuple(out.shape), tuple(I.shape)))
+    nrows, ncols, F = _dims(I)
+    capi.call("pdeip_gauss_dev", _stream(), I.data_ptr(), nrows, ncols, F, float(sigma), out.data_ptr())
+    return out
+
+
+def structure_tensor(I, sigma, rho, J):
+    """J [3, ncols, nrows] = G_rho * (sum over the channels of grad(v) grad(v)'), v = G_sigma * I: J11, J12, J22."""
+    _chk(I, J)
+    nrows, ncols, C = _dims(I)
+    if tuple(J.shape) != (3, ncols, nrows):
+        raise capi.PdeipError(capi.PDEIP_ERR_ARG, "structure_tensor: J is %s, not %s" % (tuple(J.shape), (3, ncols, nrows)))
+    capi.call("pdeip_structure_tensor_dev", _stream(), I.data_ptr(), nrows, ncols, C, float(sigma), float(rho), J.data_ptr())
+
+
+def st_weights(J, params, tau, TRACE, w8):
+    """TRACE [ncols, nrows] and w8 [8, ncols, nrows] (W NW N NE E SE S SW, times tau) of the diffusion tensor of J; params: a
+    Diffusion8Params (diffusion8_params) of which mode, lambda, alpha and C are read."""
+    _chk(J, TRACE, w8)
+    nrows, ncols, _ = _dims(J)
+    if tuple(J.shape) != (3, ncols, nrows) or tuple(TRACE.shape) != (ncols, nrows) or tuple(w8.shape) != (8, ncols, nrows):
+        raise capi.PdeipError(capi.PDEIP_ERR_ARG, "st_weights: J [3, ncols, nrows], TRACE [ncols, nrows] and w8 [8, ncols, nrows] expected")
+    capi.call("pdeip_st_weights_dev", _stream(), J.data_ptr(), nrows, ncols, ctypes.addressof(params), float(tau), TRACE.data_ptr(), w8.data_ptr())
+
+
+def st_weights_padded(J, params, tau, TRACE, w8):
+    """st_weights onto planes with a one-pixel ring: TRACE [ncols + 2, nrows + 2], w8 [8, ncols + 2, nrows + 2]; TRACE = 1 and the
+    weights 0 on the ring (what a PDEsolver8 call on the image inside its ring takes: include/pdeip.h)."""
+    _chk(J, TRACE, w8)
+    nrows, ncols, _ = _dims(J)
+    if tuple(J.shape) != (3, ncols, nrows) or tuple(TRACE.shape) != (ncols + 2, nrows + 2) or tuple(w8.shape) != (8, ncols + 2, nrows + 2):
+        raise capi.PdeipError(capi.PDEIP_ERR_ARG, "st_weights_padded: J [3, ncols, nrows], TRACE [ncols+2, nrows+2] and w8 [8, ncols+2, nrows+2] expected")
+    capi.call("pdeip_st_weights_padded_dev", _stream(), J.data_ptr(), nrows, ncols, ctypes.addressof(params), float(tau), TRACE.data_ptr(),
+              w8.data_ptr())
+
+
+def st_pad(I, out, out2=None):
+    """out (and out2) [(F,) ncols + 2, nrows + 2] = I inside a one-pixel ring of its nearest pixels."""
+    _chk(I, out, *(() if out2 is None else (out2,)))
+    nrows, ncols, F = _dims(I)
+    want = tuple(I.shape[:-2]) + (ncols + 2, nrows + 2)
+    if tuple(out.shape) != want or (out2 is not None and tuple(out2.shape) != want):
+        raise capi.PdeipError(capi.PDEIP_ERR_ARG, "st_pad: the outputs must be %s" % (want,))
+    capi.call("pdeip_st_pad_dev", _stream(), I.data_ptr(), nrows, ncols, F, out.data_ptr(), None if out2 is None else out2.data_ptr())
+
+
+def st_crop(Ip, out):
+    """out [(F,) ncols, nrows] = the inside of Ip [(F,) ncols + 2, nrows + 2]."""
+    _chk(Ip, out)
+    nrows, ncols, F = _dims(out)
+    if tuple(Ip.shape) != tuple(out.shape[:-2]) + (ncols + 2, nrows + 2):
+        raise capi.PdeipError(capi.PDEIP_ERR_ARG, "st_crop: Ip is %s for an output of %s" % (tuple(Ip.shape), tuple(out.shape)))
+    capi.call("pdeip_st_crop_dev", _stream(), Ip.data_ptr(), nrows, ncols, F, out.data_ptr())
+
+
+def diffusion8(I, params, out):
+    """out = the EED / CED filtered I (pdeip_diffusion8_dev) in the library's current ordering; `out` may be I itself."""
+    _chk(I, out)
+    if out.shape != I.shape:
+        raise capi.PdeipError(capi.PDEIP_ERR_ARG, "diffusion8: out is %s but I is %s" % (tuple(out.shape), tuple(I.shape)))
+    nrows, ncols, C = _dims(I)
+    capi.call("pdeip_diffusion8_dev", _stream(), I.data_ptr(), nrows, ncols, C, ctypes.addressof(params), out.data_ptr())
+
+
 def fst_derivatives5(It0, It1, Idt, Idx, Idy):
     _chk(It0, It1, Idt, Idx, Idy)
     nrows, ncols, F = _dims(It0)

@@ -19,6 +19,7 @@ capi.MODE_RED_BLACK the parallel one).
     flow2color / flow_errors    matlab/optical_flow/flow2color.m                  colour coding; error measures (C++ only: pdeip_flow2color)
     disp_crosscheck / flow_crosscheck / stereo_maps   this library's own: left-right and forward-backward checks (pdeip_disp_crosscheck)
     TVinpaint4                  this library's own: the holes of a sparse map filled by TV inpainting (pdeip_tv_inpaint4)
+    gaussian / Diffusion8       this library's own: smoothing at a chosen scale; structure-tensor diffusion, EED and CED (pdeip_diffusion8)
 
 `Us=`, `Vs=` (param.Us / param.Vs: spatial a-priori fields, double, NaN = no constraint) and `scales=` (param.scales) are taken
 by the late-linearisation flow drivers and the disparity driver as the reference's drivers take them.
@@ -531,6 +532,48 @@ def Diffusion4_v10(I_in, as_single=False, **param):
         raise ValueError("Diffusion4_v10: I_in must be [rows, cols] or [rows, cols, C] (got %s)" % (I.shape,))
     out = np.empty(I.shape, np.float32, order="F")
     capi.call("pdeip_diffusion4", I.ctypes.data, I.shape[0], I.shape[1], I.shape[2] if I.ndim == 3 else 1, ctypes.addressof(prm),
+              out.ctypes.data)
+    return out if as_single else uint8_matlab(out)
+
+
+def _image_single(who, I_in):
+    I = np.asfortranarray(np.asarray(I_in, dtype=np.float32))
+    if I.ndim not in (2, 3):
+        raise ValueError("%s: the image must be [rows, cols] or [rows, cols, C] (got %s)" % (who, I.shape))
+    return I
+
+
+def gaussian(I, sigma):
+    """G_sigma * I per channel, separable with 'replicate' borders (pdeip_gauss): the smoothing at a chosen scale that runme.m
+    loads from a pre-smoothed file, e.g. GAC_v10a(gaussian(I, 2), PHI).  I [rows, cols(, C)] in any numeric type, taken as
+    single; returns single."""
+    I = _image_single("gaussian", I)
+    out = np.empty(I.shape, np.float32, order="F")
+    capi.call("pdeip_gauss", I.ctypes.data, I.shape[0], I.shape[1], I.shape[2] if I.ndim == 3 else 1, float(sigma), out.ctypes.data)
+    return out
+
+
+def Diffusion8(I_in, mode="ced", as_single=False, **param):
+    """Structure-tensor anisotropic diffusion of I_in [rows, cols(, C)], 0..255 data as Diffusion4_v10 takes it: mode 'ced'
+    (coherence-enhancing: smooths along the locally dominant orientation) or 'eed' (edge-enhancing: along edges, not across them).
+    The image is uploaded once and filtered by one pdeip_diffusion8_dev call in the library's current ordering.  param: sigma, rho,
+    lambda (pass **{"lambda": v} or lambda_=v), alpha, C, tau, iters, inner_iter, omega, solver; defaults in include/pdeip.h.
+    Returns uint8(Iout) by MATLAB's rule, or the single Iout with as_single=True."""
+    prm = dev.diffusion8_params(mode, "Diffusion8", **param)
+    I = _image_single("Diffusion8", I_in)
+    t = dev.to_device(I)
+    dev.diffusion8(t, prm, t)
+    dev.sync_check()
+    out = dev.to_matlab(t)
+    return out if as_single else uint8_matlab(out)
+
+
+def capi_Diffusion8(I_in, mode="ced", as_single=False, **param):
+    """pdeip_diffusion8 on a MATLAB-shaped numpy array: the host-pointer twin of Diffusion8 above, same bits."""
+    prm = dev.diffusion8_params(mode, "capi_Diffusion8", **param)
+    I = _image_single("capi_Diffusion8", I_in)
+    out = np.empty(I.shape, np.float32, order="F")
+    capi.call("pdeip_diffusion8", I.ctypes.data, I.shape[0], I.shape[1], I.shape[2] if I.ndim == 3 else 1, ctypes.addressof(prm),
               out.ctypes.data)
     return out if as_single else uint8_matlab(out)
 

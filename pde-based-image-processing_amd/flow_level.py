@@ -231,6 +231,38 @@ class TvLevel:
         return X
 
 
+class Diffusion8Level:
+    """Structure-tensor anisotropic diffusion (EED / CED) as the stage calls pdeip_diffusion8_dev makes, composed here: per
+    iteration the structure tensor of the estimate, the weights and TRACE on planes with a one-pixel ring, the estimate inside its
+    ring as iterate and as B, per channel one PDEsolver8 call in place on the ringed iterate, and the insides back.  Planes
+    [C, ncols, nrows] or [ncols, nrows].  param: sigma, rho, tau, iters, inner_iter, omega, solver and the mode's lambda | alpha, C,
+    all given."""
+
+    def __init__(self, mode, param, order=capi.MODE_EXACT_ORDER):
+        self.kind, self.p, self.order = mode, dict(param), order
+
+    def run(self, Iin, Iout=None):
+        p = self.p
+        out = Iin.clone() if Iout is None else Iout
+        if out is not Iin:
+            out.copy_(Iin)
+        planes = out if out.dim() == 3 else out[None]
+        C, ncols, nrows = planes.shape
+        new = lambda *shape: torch.empty(shape, dtype=out.dtype, device=out.device)  # noqa: E731
+        J, TRACE, w8 = new(3, ncols, nrows), new(ncols + 2, nrows + 2), new(8, ncols + 2, nrows + 2)
+        X, B = new(C, ncols + 2, nrows + 2), new(C, ncols + 2, nrows + 2)
+        rule = dev.diffusion8_params(self.kind, **{k: p[k] for k in ("lambda", "alpha", "C") if k in p})
+        solve = dev.pde_sor8 if int(p["solver"]) == 1 else dev.pde_alr8
+        for _ in range(max(int(p["iters"]), 0)):
+            dev.structure_tensor(planes, p["sigma"], p["rho"], J)
+            dev.st_weights_padded(J, rule, p["tau"], TRACE, w8)
+            dev.st_pad(planes, X, B)
+            for c in range(C):
+                solve(X[c], TRACE, B[c], *w8, int(p["inner_iter"]), float(p["omega"]), self.order)
+            dev.st_crop(X, planes)
+        return out
+
+
 class Tv4Level:
     """The 4-neighbour denoiser's loop (matlab/denoising/TVdenoise4.m:82-103): outer_iter + 1 times DiffWeights, PsiData/TRACE/B,
     PDEsolver4.  param: alpha, omega, outer_iter, inner_iter, solver."""
