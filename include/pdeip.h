@@ -1249,7 +1249,9 @@ int pdeip_flow_interpolate(const float *I0, const float *I1, int channels, const
  * every stage.  Planes are single, column-major [nrows x ncols x frames]; x runs along the columns, y down the rows.
  *
  * pdeip_gauss_taps (host only, no HIP call): R = ceil(3 sigma) and the 2R + 1 taps g[k] = exp(-k^2 / (2 sigma^2)), k = -R..R, in
- * double, divided by their double sum (added in ascending k), each rounded to single; sigma = 0: R = 0 and the tap 1.
+ * double, divided by their double sum (added in ascending k), each rounded to single; sigma = 0: R = 0 and the tap 1.  The
+ * ceiling is that of the exact product: sigma = 32 / 3 as a double has R = 32, the next double above it needs 33 and is refused
+ * (its double product rounds to 32.0).  A sigma whose square underflows (1e-200) has R = 1 and the taps 0, 1, 0.
  * PDEIP_ERR_ARG: sigma NaN, negative or infinite, capacity < 2R + 1 (nothing written); PDEIP_ERR_UNSUPPORTED: R > 32.
  *
  * pdeip_gauss / pdeip_gauss_dev: out = G_sigma * in, separable, border 'replicate'.  Pass 1 runs along the rows (down a column)
@@ -1278,7 +1280,11 @@ int pdeip_flow_interpolate(const float *I0, const float *I1, int channels, const
  *   the eight weights by TVdenoise8's assembly with dyy := D11, dxx := D22, dxy := D12 (wW = (D11 + D11 of the west pixel) / 2, wN =
  *   (D22 + D22 north) / 2, wNW = (D12 + D12 north-west) / 4, wNE = -(D12 + D12 north-east) / 4, and so on), a weight across the
  *   frame's edge zero; sum = ((wW + wNW) + wN) + ... + wSW; w8[k] = (float)(tau w_k), TRACE = (float)(1 + tau sum).
- * A NaN in J fails every comparison above (a flat pixel's tensor).  Only mode, lambda, alpha and C of `prm` are read (NaN or
+ * A NaN in J fails every comparison above (a flat pixel's tensor).  An Inf in j11 or j22 passes them: r = Inf, c2 = Inf / Inf = NaN and s2 =
+ * 2 j12 / Inf = 0, so D11 and D22 of that pixel are NaN and D12 is finite: TRACE and the four axial weights (W, N, E, S) are NaN at
+ * the pixel and TRACE and the one axial weight that reads it at each of its four axial neighbours (5 NaN in TRACE, 2 in each axial
+ * plane for an interior pixel), the diagonal weights stay finite.  The weights across the frame's edge are zero by selection, not
+ * by a product, so a non-finite tensor on one edge of the frame leaves the opposite edge as it was.  Only mode, lambda, alpha and C of `prm` are read (NaN or
  * prm == NULL: the defaults below); tau is the argument.  1 launch.  Refused before any HIP call: a NULL plane, a frame below 3x3,
  * more than 65535 columns, an unknown mode, lambda <= 0 or not finite (EED), alpha outside [0, 1], C <= 0 or not finite (CED), tau
  * NaN, negative or infinite.

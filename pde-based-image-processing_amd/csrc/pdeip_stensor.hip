@@ -22,7 +22,11 @@ constexpr int MAX_GRID_YZ = 65535; // the column (or a block of columns) is bloc
 int taps_of(const char *who, const char *name, double sigma, GaussTaps *T)
 {
     if (!std::isfinite(sigma) || sigma < 0.0) return set_err(PDEIP_ERR_ARG, "%s: %s must be finite and >= 0 (got %g)", who, name, sigma);
-    const double r = std::ceil(3.0 * sigma);
+    // ceil of the exact product: where the double 3 sigma rounds down onto an integer the radius is the next one (the smallest sigma
+    // above 32 / 3 gives the double 32.0 and needs 33 taps)
+    const double p3 = 3.0 * sigma;
+    double r = std::ceil(p3);
+    if (r == p3 && std::fma(3.0, sigma, -p3) > 0.0) r += 1.0;
     if (r > (double)GAUSS_RMAX)
         return set_err(PDEIP_ERR_UNSUPPORTED, "%s: %s = %g needs a radius of %.0f taps (at most %d)", who, name, sigma, r, GAUSS_RMAX);
     const int R = (int)r;

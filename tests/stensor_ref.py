@@ -7,6 +7,7 @@ with every operation rounded in the stated order (numpy forms no FMA); the diffu
 float32 J, rounded to float32 at the end.  One step's solve is oracle_lib.PDEsolver8, the reference's own solver.
 """
 import math
+from fractions import Fraction
 
 import numpy as np
 
@@ -29,15 +30,18 @@ def params(mode="ced", **param):
 # ---- Gaussian ---------------------------------------------------------------------------------------------------------------
 
 def radius(sigma):
-    return int(math.ceil(3.0 * sigma))
+    """ceil(3 sigma) of the exact product (the double product may round down onto an integer that the exact one exceeds)."""
+    return int(math.ceil(3 * Fraction(sigma)))
 
 
 def taps(sigma):
-    """g[k] = exp(-k^2 / (2 sigma^2)), k = -R..R, in double, over their double sum (ascending k), each rounded to float32."""
+    """g[k] = exp(-k^2 / (2 sigma^2)), k = -R..R, in double, over their double sum (ascending k), each rounded to float32.  A sigma
+    whose square underflows to zero divides by it as IEEE does: exp(-inf) = 0, the centre tap alone."""
     R = radius(sigma)
     if R > RMAX:
         raise ValueError("sigma = %g needs a radius above %d" % (sigma, RMAX))
-    g = [1.0 if k == 0 else math.exp(-float(k * k) / (2.0 * sigma * sigma)) for k in range(-R, R + 1)]
+    den = 2.0 * sigma * sigma
+    g = [1.0 if k == 0 else (math.exp(-float(k * k) / den) if den > 0.0 else 0.0) for k in range(-R, R + 1)]
     s = 0.0
     for v in g:
         s += v
@@ -148,6 +152,27 @@ def diffusion_tensor(J, mode, p):
             l2 = np.ones_like(r)
         m, h = 0.5 * (l1 + l2), 0.5 * (l1 - l2)
         return m + h * c2, m - h * c2, h * s2
+
+
+def exp_terms(J, mode, p):
+    """(taken, value): where diffusion_tensor() takes an exp (CED: r > 0, EED: mu1 > 0) and what numpy's exp returns there, from the
+    same float64 operations in the same order; `value` is NaN where none is taken."""
+    j11, j12, j22 = (np.asarray(J[:, :, k], F32).astype(np.float64) for k in range(3))
+    with np.errstate(all="ignore"):
+        s, d = j11 + j22, j11 - j22
+        r = np.sqrt(d * d + 4.0 * j12 * j12)
+        mu1 = 0.5 * (s + r)
+        if mode == "ced":
+            taken = r > 0.0
+            rs = np.where(taken, r, 1.0)
+            value = np.exp(-float(p["C"]) / (rs * rs))
+        else:
+            taken = mu1 > 0.0
+            lam = float(p["lambda"])
+            q = np.where(taken, mu1, 1.0) / (lam * lam)
+            q2 = q * q
+            value = np.exp(-3.31488 / (q2 * q2))
+    return taken, np.where(taken, value, np.nan)
 
 
 def _shift(A, di, dj):
