@@ -96,6 +96,14 @@ int pdeip_get_devices(int *ids, int capacity);
 int pdeip_release(void);
 /* Number of kernel launches the last *_dev solver call enqueued (diagnostic). */
 int pdeip_last_launch_count(void);
+/* Diagnostic: the direction of every launch of the calling thread's last red-black point-SOR *_dev call that ran the launch chain
+ * (families 3 and 4 of pdeip_debug_plan_sor), in order: the mirror mode the launch ran with -- 0 every strip marched west -> east,
+ * 2 every strip east -> west, 1 the odd strips east -> west; 0 for the chain's kernels that have no mirrored march.  Writes the
+ * first `cap` of them to out (may be NULL with cap 0) and returns their number; 0 after any other point-SOR call.  With
+ * PDEIP_RBP_SERPENTINE=3, and with the variable absent on frames whose planes exceed the Infinity Cache (13 * pixels * frames * 4
+ * bytes > 256 MiB), the k_sor_rbp launches on a device alternate 0, 2, 0, 2, ... across launches AND calls (each starts where the
+ * one before ended, on lines the cache still holds); every direction gives the same bits. */
+int pdeip_debug_last_directions(int *out, int cap);
 /* Changes whenever the library frees or regrows a cached workspace buffer (a larger frame, pdeip_release, pdeip_set_device).
  * A caller that captured *_dev calls into a HIP graph must re-capture when the value differs from the one at capture time:
  * the graph's kernel arguments point into those buffers.  Replaying a captured graph between eager calls is supported: nothing

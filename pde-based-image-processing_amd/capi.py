@@ -212,6 +212,7 @@ SIGNATURES = {
     "pdeip_get_devices": [ctypes.POINTER(ctypes.c_int), _I],
     "pdeip_release": [],
     "pdeip_last_launch_count": [],
+    "pdeip_debug_last_directions": [ctypes.POINTER(ctypes.c_int), _I],
     "pdeip_workspace_generation": [],
     "pdeip_persist_error": [],
     "pdeip_debug_persist_order": [_I, _I, _I, ctypes.POINTER(ctypes.c_int)],

@@ -311,6 +311,13 @@ extern "C" int pdeip_release(void)
     return PDEIP_OK;
 }
 extern "C" int pdeip_last_launch_count(void) { return tls.last_launches; }
+extern "C" int pdeip_debug_last_directions(int *out, int cap)
+{
+    const int n = (int)tls.last_directions.size();
+    for (int k = 0; k < n && k < cap; k++)
+        if (out) out[k] = tls.last_directions[k];
+    return n;
+}
 extern "C" int pdeip_workspace_generation(void) { return g.ws_generation; }
 extern "C" int pdeip_persist_error(void)
 { // waits for the device(s), then reports whether a bounded spin of the persistent kernel timed out

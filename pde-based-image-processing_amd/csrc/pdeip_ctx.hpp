@@ -38,6 +38,10 @@ struct DeviceState {
     std::map<const void *, size_t> lds_opt_in; // kernel -> dynamic LDS bytes opted into (hipFuncSetAttribute is per device)
     std::map<const void *, int> resident_waves; // kernel -> waves the device holds at once (occupancy query)
     hipStream_t worker_stream = nullptr; // the stream a worker thread of a slab-split host call uses on this device (pdeip_multi.hip)
+    // The last k_sor_rbp launch on this device marched its strips west -> east and ended at their east ends: under
+    // PDEIP_RBP_SERPENTINE=3 the next one marches east -> west, starting on the lines the Infinity Cache still holds
+    // (pdeip_sor_plan.hpp).  Only a traversal order: whatever it holds, the results are the same bits.
+    bool rbp_next_mirror = false;
     void reset_caches()
     {
         persist_used = false;
@@ -50,6 +54,7 @@ struct DeviceState {
 struct ThreadState {
     char err[512] = "";
     int last_launches = 0;
+    std::vector<int> last_directions; // point SOR: the mirror mode (0 / 1 / 2) each launch of the last call ran with, 0 for kernels that have none
     int dev_slot = -1; // >= 0: cur_dev() returns this slot of Context::devs instead of the current HIP device's (virtual-thread test mode)
 };
 extern thread_local ThreadState tls;

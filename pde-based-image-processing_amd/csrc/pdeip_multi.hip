@@ -204,6 +204,7 @@ int multi_sor(const MultiCall &mc, int *handled)
     }
     (void)hipSetDevice(g.group[0]);
     tls.last_launches = 0;
+    tls.last_directions.clear(); // the slabs' launches are their workers': each worker's device slot keeps its own direction bit
     for (int ti = 0; ti < nth; ti++) tls.last_launches += launches[ti];
     for (int ti = 0; ti < nth; ti++)
         if (rc[ti] != PDEIP_OK) return set_err(rc[ti], "%s", errs[ti][0] ? errs[ti] : "multi-device call failed");

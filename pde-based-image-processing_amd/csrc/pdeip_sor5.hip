@@ -167,15 +167,17 @@ template <class Mdl> int run_chain(const SweepCall<Mdl> &c, const SorPlan &plan,
     hipStream_t s = c.s;
     SweepTimer timer(s, PDEIP_TIMER_MARKERS ? 0 : plan.nlaunch); // the events ride on the first and the last launch: no packet of their own
     int done = 0; // sweeps
+    DeviceState *d = cur_dev();
     RC(for_each_launch(plan, [&](const SorLaunch &l) {
         bind_buffers<Mdl>(P, buf, l);
         hipEvent_t const e0 = timer.start_for(l.index), e1 = timer.stop_for(l.index);
+        const int mirror = l.kind == K_RBP ? resolve_mirror(plan.mirror_mode, d->rbp_next_mirror) : 0;
         if (l.kind == K_RBP) {
             RC(ensure_lds(reinterpret_cast<const void *>(rbp_kernel<Mdl>(l.first)), PL::LDS_BYTES));
             // the derived planes leave the kernel only if a later launch of this call reads them
             const bool keep = l.first && done + PS < c.iter;
             launch_timed(rbp_kernel<Mdl>(l.first), dim3((unsigned)l.gridx, (unsigned)c.nframes), dim3(PL::THREADS), PL::LDS_BYTES, s, e0, e1, P, keep ? c.aux0 : nullptr,
-                         keep ? c.aux1 : nullptr, c.nrows, c.ncols, l.tj, l.tiles, l.units, c.omega, c.col0, c.n, plan.mirror_mode);
+                         keep ? c.aux1 : nullptr, c.nrows, c.ncols, l.tj, l.tiles, l.units, c.omega, c.col0, c.n, mirror);
         } else { // the first launch also builds the divisor planes
             launch_timed(rb_kernel<Mdl>(plan.vec, l.first, l.sweeps == 2), dim3((unsigned)l.gridx, (unsigned)c.nframes), dim3(64 * RB_WAVES_PER_BLOCK), 0, s, e0, e1, P,
                          l.first ? c.aux0 : nullptr, l.first ? c.aux1 : nullptr, c.nrows, c.ncols, l.tj, l.tiles, l.units, c.omega, c.col0, c.n);
@@ -186,6 +188,7 @@ template <class Mdl> int run_chain(const SweepCall<Mdl> &c, const SorPlan &plan,
         }
         done += l.sweeps;
         tls.last_launches++;
+        tls.last_directions.push_back(mirror);
         return PDEIP_OK;
     }));
     timer.stop(plan.nlaunch);
@@ -207,6 +210,7 @@ int run_sweeps(hipStream_t s, SweepPlanes<Mdl> P, int nrows, int ncols, int nfra
     constexpr int NIT = Mdl::NIT;
     const size_t n = (size_t)nrows * ncols;
     tls.last_launches = 0;
+    tls.last_directions.clear();
     bool same = dst != nullptr, aligned = true; // dst == it_out: in place
     for (int f = 0; f < NIT; f++) {
         same = same && dst[f] == P.it_out[f];
@@ -449,6 +453,7 @@ extern "C" int pdeip_disp_sor_llin_sym4_dev(void *stream, const float *U0, float
     const float *U[2] = {U0, U1}, *cf[2][6] = {{Cu0, Du0, wW0, wN0, wE0, wS0}, {Cu1, Du1, wW1, wN1, wE1, wS1}};
     float *dU[2] = {dU0, dU1};
     int launches = 0;
+    std::vector<int> directions; // of both fields' launches, in order
     for (int k = 0; k < 2; k++) {
         if (solver == PDEIP_SOLVER_ALR) {
             RC(pdeip_disp_alr_llin4_dev(stream, U[k], dU[k], cf[k][0], cf[k][1], cf[k][2], cf[k][3], cf[k][4], cf[k][5], nrows, ncols, iter, omega, mode));
@@ -458,10 +463,12 @@ extern "C" int pdeip_disp_sor_llin_sym4_dev(void *stream, const float *U0, float
             P.ro[0] = U[k];
             for (int f = 0; f < 6; f++) P.cf[f] = cf[k][f];
             RC(run_sweeps<ModelDispSym4>(s, P, nrows, ncols, 1, iter, omega, mode, col0));
+            directions.insert(directions.end(), tls.last_directions.begin(), tls.last_directions.end());
         }
         launches += tls.last_launches;
     }
     tls.last_launches = launches;
+    tls.last_directions = directions;
     return PDEIP_OK;
 }
 

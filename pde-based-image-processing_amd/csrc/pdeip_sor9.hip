@@ -124,6 +124,7 @@ extern "C" int pdeip_pde_sor8_dev(void *stream, float *X, const float *TRACE, co
     RC(check_dims(who, nrows, ncols, nframes));
     RC(check_mode(who, mode));
     tls.last_launches = 0;
+    tls.last_directions.clear(); // the nine-point kernels have no mirrored march
     Pde8Call c{static_cast<hipStream_t>(stream), X, {B, TRACE, wW, wNW, wN, wNE, wE, wSE, wS, wSW}, nullptr, nullptr, nrows, ncols, nframes, iter, omega, col0,
                (size_t)nrows * ncols};
     bool aligned = aligned16(X);

@@ -19,6 +19,7 @@ enum { FORM_NONE = 0, FORM_PERSIST, FORM_WALK, FORM_FRONT };             // exac
 enum { K_RBP = 1, K_RB2, K_RB1, K_SMALL, K_P8C2, K_P8C1, K_PACK, K_PERSIST, K_WALK, K_DERIVE, K_FRONT, K_BORDERS }; // kernel of a launch
 enum { BUF_CALLER = 0, BUF_SCRATCH, BUF_DST };
 constexpr int RBP_SWEEPS = 4; // sweeps per launch of the pipeline (k_sor_rbp)
+constexpr int MIRROR_ALTERNATE = 3; // PDEIP_RBP_SERPENTINE: every other k_sor_rbp launch on a device marches every strip backwards
 
 // What the planner knows of a model (sor_traits<Mdl>() in pdeip_sor5.hip, PDE8_TRAITS in pdeip_sor9.hip).
 struct SorTraits {
@@ -40,7 +41,7 @@ struct SorShape {
 // PDEIP_* of the environment (read_sor_knobs).
 struct SorKnobs {
     bool persist = true, walk = false, small = true, fuse = true, pipe = true;
-    int small_q = 1, rb_tj = 0, rbp_tj = 0, serpentine = 0;
+    int small_q = 1, rb_tj = 0, rbp_tj = 0, serpentine = 0; // serpentine -1: PDEIP_RBP_SERPENTINE absent, the frame decides
 };
 // cus: compute units; rb2_slots: resident waves of the two-sweep march; rbp_slots: resident workgroups of k_sor_rbp.  A fact that is
 // 0 is not known yet: the planner asks for it -- ask(FACT_*) returns it -- only where the call's path needs it, as a call always has
@@ -56,7 +57,7 @@ struct SorPlan {
     int nsteps = 0, nlaunch = 0;                 // nlaunch: what pdeip_last_launch_count() reports
     SorLaunch step[4] = {};
     bool has_dst = false, vec = false;
-    int mirror_mode = 0;        // k_sor_rbp: PDEIP_RBP_SERPENTINE, clamped to 0..2
+    int mirror_mode = 0;        // k_sor_rbp: PDEIP_RBP_SERPENTINE, 0..3; what a launch runs with is resolve_mirror()'s answer
     bool copy_in = false;       // the caller's iterate is copied to the destination first (exact order relaxes there; iter <= 0)
     bool copy_back = false;     // in place and the last launch wrote the scratch copy
     bool persist_setup = false; // k_persist_setup runs in front of the walker (not counted)
@@ -89,9 +90,16 @@ inline void read_sor_knobs(SorKnobs &k, int set, bool pde8 = false)
     } else { // a call that launches the pipeline
         k.rbp_tj = env_int("PDEIP_RBP_TJ", 0);
         // 1: alternate strips march backwards (k_sor_rbp, `mirror_mode`), 2: every strip (tests).  Same bits; at 4K the launch is
-        // not faster for the halo columns neighbours then share (97.7 vs 94.6 us): the pipeline's step sets its time.  Off.
-        const int serp = env_int("PDEIP_RBP_SERPENTINE", 0);
-        k.serpentine = serp < 0 || serp > 2 ? 0 : serp;
+        // not faster for the halo columns neighbours then share (97.7 vs 94.6 us): the pipeline's step sets its time.
+        // 3: alternate whole LAUNCHES (resolve_mirror).  A launch ends at the east end of every strip, and those are the lines the
+        // Infinity Cache holds when the next launch -- of this call or of the next one -- begins: marched east -> west it starts on
+        // hits instead of evicting them before it gets there.  Elin4 4K, iter = 4 per call: 98.3 -> 84.8 and 95.2 -> 85.0 us per
+        // step on two devices (tools/time_rbp_alternate.py, profiles/NOTES.md R6.1).  A value that is present is obeyed as it
+        // stands; absent (-1 here), the frame decides (default_mirror).
+        const char *serp = getenv("PDEIP_RBP_SERPENTINE");
+        const bool set = serp && *serp;
+        const int v = set ? atoi(serp) : 0;
+        k.serpentine = !set ? -1 : (v < 0 || v > MIRROR_ALTERNATE ? 0 : v);
     }
 }
 
@@ -219,6 +227,15 @@ template <class Ask> inline void plan_chain(SorPlan &p, const SorTraits &t, cons
     p.copy_back = !sh.has_dst && (p.nlaunch & 1);
 }
 
+// The mirror mode of a call that does not set PDEIP_RBP_SERPENTINE: launches alternate (3) where the planes of a launch -- thirteen
+// for the flow model the rule was measured on, 13 * pixels * frames * 4 bytes -- exceed the 256 MiB of the Infinity Cache, and all
+// march forwards (0) below.  Where everything stays resident between launches there is nothing to win back, and a mirrored launch
+// by itself was up to 3 % slower than a forward one at 1080p (33.2 vs 32.3 us on one of two devices: NOTES R6.1).
+inline int default_mirror(const SorShape &sh)
+{
+    return (size_t)13 * sh.nrows * sh.ncols * sh.nframes * sizeof(float) > ((size_t)256 << 20) ? MIRROR_ALTERNATE : 0;
+}
+
 // The planner reads the knobs (and nothing else outside its arguments) and makes no HIP call; `ask` may.
 template <class Ask> inline SorPlan plan_sor(const SorTraits &t, const SorShape &sh, const SorDevice &dev, Ask &&ask)
 {
@@ -235,10 +252,23 @@ template <class Ask> inline SorPlan plan_sor(const SorTraits &t, const SorShape 
         if (t.pde8 || !k.small || !plan_small(p, t, sh, k, dev.cus, ask)) {
             read_sor_knobs(k, KNOBS_CHAIN, t.pde8);
             plan_chain(p, t, sh, k, dev, ask);
-            p.mirror_mode = k.serpentine;
+            p.mirror_mode = k.serpentine >= 0 ? k.serpentine : default_mirror(sh);
         }
     }
     return p;
+}
+
+// The mirror mode one k_sor_rbp launch runs with (0, 1 or 2), from the plan's mode and the device's bit (DeviceState::rbp_next_mirror),
+// set while the device's last pipeline launch ended at the east ends of its strips.  Mode 3 mirrors the launch when the bit is
+// set; modes 0 .. 2 are obeyed as they stand.  Either way the bit then says where THIS launch ends (mode 1, half the strips
+// each way, counts as forward), so under mode 3 it flips with every launch: launches 2, 3, ... of a call and the first launch
+// of the next call each start where the one before ended.  Every direction gives the same bits (pdeip_sor_rbp.hpp), so neither
+// the bit's history nor a direction frozen into a captured graph can change a result.
+inline int resolve_mirror(int mode, bool &next_mirror)
+{
+    const int m = mode == MIRROR_ALTERNATE ? (next_mirror ? 2 : 0) : mode;
+    next_mirror = m != 2;
+    return m;
 }
 
 // Calls fn(launch) for every launch of the plan, in order.  Launch i of a ping-pong chain reads what launch i - 1 wrote.  In
