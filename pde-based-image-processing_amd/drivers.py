@@ -29,6 +29,7 @@ MATLAB session the toolbox runs in; the `capi_*` functions at the end of this fi
 `graph=True` (the llin flow drivers and the FAS driver, parallel orderings): the run's launches are captured into a HIP graph
 on the first call for a frame size and replayed afterwards (graphs.py) -- same kernels and bits, no per-launch host work.
 """
+import contextlib
 import ctypes
 import math
 
@@ -311,18 +312,33 @@ def TVdenoise4(I_in, mode=capi.MODE_EXACT_ORDER, **param):
     return _tv(I_in, fl.Tv4Level, p, pyramid.gaussian(7, 2.0), smooth_last=True)
 
 
-# ---- the same two drivers through the C-ABI (what the MEX stubs call): host arrays in, host arrays out ----------------------
+# ---- the same eight drivers through the C-ABI (what the MEX stubs call): host arrays in, host arrays out --------------------
 _TERM = {"NONE": 0, "RGB": 1, "GRAD": 2, "GRADMAG": 3}
 
 
-def _c_params(param):
+def _c_struct(double_fields, int_fields, param):
+    """A parameter struct of include/pdeip.h (its doubles, then its ints) filled from `param`; 0, as for a name left out: the driver's default."""
     class P(ctypes.Structure):
-        _fields_ = [(k, ctypes.c_double) for k in ("alpha", "omega", "gammaS", "b1", "b2", "scl_factor")] + \
-                   [(k, ctypes.c_int) for k in ("firstLoop", "secondLoop", "iter", "solver", "scales")]
+        _fields_ = [(k, ctypes.c_double) for k in double_fields] + [(k, ctypes.c_int) for k in int_fields]
     s = P()
     for k, _ in P._fields_:
         setattr(s, k, type(getattr(s, k))(param.get(k, 0) or 0))
     return s
+
+
+def _c_params(param):   # pdeip_driver_params
+    return _c_struct(("alpha", "omega", "gammaS", "b1", "b2", "scl_factor"), ("firstLoop", "secondLoop", "iter", "solver", "scales"), param)
+
+
+@contextlib.contextmanager
+def _ordering(mode):
+    """The library's sweep ordering set to `mode` for one C-ABI call, then put back."""
+    old = capi.get_mode()
+    capi.set_mode(mode)
+    try:
+        yield
+    finally:
+        capi.set_mode(old)
 
 
 def _f_single(a):
@@ -334,60 +350,43 @@ def _f_double(a):
     return None if a is None else np.asfortranarray(np.asarray(a, dtype=np.float64))
 
 
+def _ptr(a):
+    return None if a is None else a.ctypes.data
+
+
+def _flow_out(I):
+    rows, cols = I.shape[:2]
+    return rows, cols, np.zeros((rows, cols), np.float32, order="F"), np.zeros((rows, cols), np.float32, order="F")
+
+
 def capi_FlowEminND_llin_2D_v10(Iin, channels, fstTerm="rgb", sndTerm="none", mode=capi.MODE_EXACT_ORDER, Us=None, Vs=None, **param):
     """pdeip_flow_nd_llin on MATLAB-shaped numpy arrays: the C++ twin of FlowEminND_llin_2D_v10 above, same bits."""
-    I = _f_single(Iin)
-    rows, cols = I.shape[:2]
-    U, V = np.zeros((rows, cols), np.float32, order="F"), np.zeros((rows, cols), np.float32, order="F")
-    us, vs = _f_double(Us), _f_double(Vs)
-    prm = _c_params(param)
-    old = capi.get_mode()
-    capi.set_mode(mode)
-    try:
+    I, us, vs, prm = _f_single(Iin), _f_double(Us), _f_double(Vs), _c_params(param)
+    rows, cols, U, V = _flow_out(I)
+    with _ordering(mode):
         capi.call("pdeip_flow_nd_llin", I.ctypes.data, rows, cols, int(channels), _TERM[fstTerm.upper()], _TERM[sndTerm.upper()], ctypes.addressof(prm),
-                  None if us is None else us.ctypes.data, None if vs is None else vs.ctypes.data, U.ctypes.data, V.ctypes.data)
-    finally:
-        capi.set_mode(old)
+                  _ptr(us), _ptr(vs), U.ctypes.data, V.ctypes.data)
     return U, V
 
 
 def capi_DispEminND_llin_2D(Il, Ir, fstTerm="rgb", sndTerm="none", mode=capi.MODE_EXACT_ORDER, Us=None, **param):
     """pdeip_disp_nd_llin on MATLAB-shaped numpy arrays."""
-    L, R = _f_single(Il), _f_single(Ir)
+    L, R, us, prm = _f_single(Il), _f_single(Ir), _f_double(Us), _c_params(param)
     rows, cols, C = L.shape
     U = np.zeros((rows, cols), np.float32, order="F")
-    us = _f_double(Us)
-    prm = _c_params(param)
-    old = capi.get_mode()
-    capi.set_mode(mode)
-    try:
+    with _ordering(mode):
         capi.call("pdeip_disp_nd_llin", L.ctypes.data, R.ctypes.data, rows, cols, C, _TERM[fstTerm.upper()], _TERM[sndTerm.upper()], ctypes.addressof(prm),
-                  None if us is None else us.ctypes.data, U.ctypes.data)
-    finally:
-        capi.set_mode(old)
+                  _ptr(us), U.ctypes.data)
     return U
-
-
-def _c_tv_params(param):
-    class P(ctypes.Structure):
-        _fields_ = [(k, ctypes.c_double) for k in ("alpha", "omega", "scl", "scl_factor")] + [(k, ctypes.c_int) for k in ("outer_iter", "inner_iter", "solver")]
-    s = P()
-    for k, _ in P._fields_:
-        setattr(s, k, type(getattr(s, k))(param.get(k, 0) or 0))
-    return s
 
 
 def _capi_tv(entry, I_in, mode, param):
     I = _f_single(I_in)
     rows, cols, F = I.shape
     out = np.zeros((rows, cols, F), np.float32, order="F")
-    prm = _c_tv_params(param)
-    old = capi.get_mode()
-    capi.set_mode(mode)
-    try:
+    prm = _c_struct(("alpha", "omega", "scl", "scl_factor"), ("outer_iter", "inner_iter", "solver"), param)   # pdeip_tv_params
+    with _ordering(mode):
         capi.call(entry, I.ctypes.data, rows, cols, F, ctypes.addressof(prm), out.ctypes.data)
-    finally:
-        capi.set_mode(old)
     return out if np.asarray(I_in).ndim == 3 else out[:, :, 0]
 
 
@@ -403,74 +402,41 @@ def capi_TVdenoise4(I_in, mode=capi.MODE_EXACT_ORDER, **param):
 
 def capi_FlowEminHS_elin_2D_v10(Iin, channels, mode=capi.MODE_EXACT_ORDER, **param):
     """pdeip_flow_hs_elin: the C++ twin of FlowEminHS_elin_2D_v10 above, same bits."""
-    I = _f_single(Iin)
-    rows, cols = I.shape[:2]
-    U, V = np.zeros((rows, cols), np.float32, order="F"), np.zeros((rows, cols), np.float32, order="F")
-    prm = _c_params(param)
-    old = capi.get_mode()
-    capi.set_mode(mode)
-    try:
+    I, prm = _f_single(Iin), _c_params(param)
+    rows, cols, U, V = _flow_out(I)
+    with _ordering(mode):
         capi.call("pdeip_flow_hs_elin", I.ctypes.data, rows, cols, int(channels), ctypes.addressof(prm), U.ctypes.data, V.ctypes.data)
-    finally:
-        capi.set_mode(old)
     return U, V
 
 
 def capi_DispEminND_llin_sym_2D(Il, Ir, mode=capi.MODE_EXACT_ORDER, **param):
     """pdeip_disp_nd_llin_sym: the C++ twin of DispEminND_llin_sym_2D above, same bits; -> U [nrows, ncols, 2]."""
-    class P(ctypes.Structure):
-        _fields_ = [(k, ctypes.c_double) for k in ("alpha", "beta", "omega", "b1", "b2", "scl_factor")] + \
-                   [(k, ctypes.c_int) for k in ("firstLoop", "secondLoop", "iter", "solver")]
-    prm = P()
-    for k, _ in P._fields_:
-        setattr(prm, k, type(getattr(prm, k))(param.get(k, 0) or 0))
+    prm = _c_struct(("alpha", "beta", "omega", "b1", "b2", "scl_factor"), ("firstLoop", "secondLoop", "iter", "solver"), param)   # pdeip_sym_params
     L, R = _f_single(Il), _f_single(Ir)
     rows, cols, C = L.shape
     U = np.zeros((rows, cols, 2), np.float32, order="F")
-    old = capi.get_mode()
-    capi.set_mode(mode)
-    try:
+    with _ordering(mode):
         capi.call("pdeip_disp_nd_llin_sym", L.ctypes.data, R.ctypes.data, rows, cols, C, ctypes.addressof(prm), U.ctypes.data)
-    finally:
-        capi.set_mode(old)
     return U
 
 
 def capi_FlowEminAD_llin_2D_v10(Iin, channels, fstTerm="rgb", sndTerm="none", mode=capi.MODE_EXACT_ORDER, Us=None, Vs=None, quantile=0.0, diffusion="image", **param):
     """pdeip_flow_ad_llin: the C++ twin of FlowEminAD_llin_2D_v10 above, same bits."""
-    I = _f_single(Iin)
-    rows, cols = I.shape[:2]
-    U, V = np.zeros((rows, cols), np.float32, order="F"), np.zeros((rows, cols), np.float32, order="F")
-    us, vs = _f_double(Us), _f_double(Vs)
-    prm = _c_params(param)
-    old = capi.get_mode()
-    capi.set_mode(mode)
-    try:
+    I, us, vs, prm = _f_single(Iin), _f_double(Us), _f_double(Vs), _c_params(param)
+    rows, cols, U, V = _flow_out(I)
+    with _ordering(mode):
         capi.call("pdeip_flow_ad_llin", I.ctypes.data, rows, cols, int(channels), _TERM[fstTerm.upper()], _TERM[sndTerm.upper()], ctypes.addressof(prm),
-                  float(quantile), int(str(diffusion).lower() == "flow"), None if us is None else us.ctypes.data, None if vs is None else vs.ctypes.data,
-                  U.ctypes.data, V.ctypes.data)
-    finally:
-        capi.set_mode(old)
+                  float(quantile), int(str(diffusion).lower() == "flow"), _ptr(us), _ptr(vs), U.ctypes.data, V.ctypes.data)
     return U, V
 
 
 def capi_FlowEminNDFASFMG_elin_2D_v10(Iin, channels, mode=capi.MODE_EXACT_ORDER, **param):
     """pdeip_flow_fas_fmg_elin: the C++ twin of FlowEminNDFASFMG_elin_2D_v10 above, same bits."""
-    class P(ctypes.Structure):
-        _fields_ = [(k, ctypes.c_double) for k in ("alpha", "omega", "b1", "b2", "scl_factor")] + \
-                   [(k, ctypes.c_int) for k in ("firstLoop", "iter", "solver", "cycle_index", "scales")]
-    prm = P()
-    for k, _ in P._fields_:
-        setattr(prm, k, type(getattr(prm, k))(param.get(k, 0) or 0))
+    prm = _c_struct(("alpha", "omega", "b1", "b2", "scl_factor"), ("firstLoop", "iter", "solver", "cycle_index", "scales"), param)   # pdeip_fas_params
     I = _f_single(Iin)
-    rows, cols = I.shape[:2]
-    U, V = np.zeros((rows, cols), np.float32, order="F"), np.zeros((rows, cols), np.float32, order="F")
-    old = capi.get_mode()
-    capi.set_mode(mode)
-    try:
+    rows, cols, U, V = _flow_out(I)
+    with _ordering(mode):
         capi.call("pdeip_flow_fas_fmg_elin", I.ctypes.data, rows, cols, int(channels), ctypes.addressof(prm), U.ctypes.data, V.ctypes.data)
-    finally:
-        capi.set_mode(old)
     return U, V
 
 
@@ -1015,13 +981,9 @@ def capi_TVinpaint4(D, guide=None, mode=capi.MODE_EXACT_ORDER, return_filled=Fal
     out = np.zeros((rows, cols, F), np.float32, order="F")
     filled = np.zeros((rows, cols, F), np.float32, order="F") if return_filled else None
     prm = dev.InpaintParams.make(**param)
-    old = capi.get_mode()
-    capi.set_mode(mode)
-    try:
-        capi.call("pdeip_tv_inpaint4", d3.ctypes.data, rows, cols, F, None if g3 is None else g3.ctypes.data, 0 if g3 is None else g3.shape[2],
-                  ctypes.addressof(prm), out.ctypes.data, None if filled is None else filled.ctypes.data)
-    finally:
-        capi.set_mode(old)
+    with _ordering(mode):
+        capi.call("pdeip_tv_inpaint4", d3.ctypes.data, rows, cols, F, _ptr(g3), 0 if g3 is None else g3.shape[2],
+                  ctypes.addressof(prm), out.ctypes.data, _ptr(filled))
     shape = (lambda a: a if d.ndim == 3 else a[:, :, 0])
     return (shape(out), shape(filled)) if return_filled else shape(out)
 
@@ -1074,15 +1036,10 @@ def flow_interpolate(I0, I1, U, V, Ub=None, Vb=None, t=0.5, return_flow=False, r
     Ut, Vt = ((np.zeros((rows, cols), np.float32, order="F") for _ in range(2)) if return_flow else (None, None))
     src = np.zeros((rows, cols), np.float32, order="F") if return_source else None
     prm = dev.InterpParams.make(**prm_kw)
-    ptr = lambda a: None if a is None else a.ctypes.data
-    old = capi.get_mode()
-    capi.set_mode(mode)
-    try:
+    with _ordering(mode):
         capi.call("pdeip_flow_interpolate", f0.ctypes.data, f1.ctypes.data, C, planes[0].ctypes.data, planes[1].ctypes.data,
-                  ptr(planes[2]) if Ub is not None else None, ptr(planes[3]) if Ub is not None else None, rows, cols, t,
-                  ctypes.addressof(prm), It.ctypes.data, ptr(Ut), ptr(Vt), ptr(src))
-    finally:
-        capi.set_mode(old)
+                  _ptr(planes[2]) if Ub is not None else None, _ptr(planes[3]) if Ub is not None else None, rows, cols, t,
+                  ctypes.addressof(prm), It.ctypes.data, _ptr(Ut), _ptr(Vt), _ptr(src))
     out = (It if i0.ndim == 3 else It[:, :, 0],)
     if return_flow:
         out += (np.stack([Ut, Vt], axis=2),)

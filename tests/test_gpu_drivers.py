@@ -236,6 +236,39 @@ def test_resident_cxx_drivers_equal_the_python_drivers(pdeip):
         D.capi_FlowEminND_llin_2D_v10(I, 1, "gradmag", "none")   # 'No such fstTerm'
 
 
+@pytest.mark.parametrize("case", ["nd_vs_only", "nd_scl06", "disp_scl06", "ad_vs_flow_diffusion", "disp_rgb_rgb_point_rb", "hs_default_iter_scl06", "disp_scales_past_shrinking"])
+def test_resident_cxx_drivers_on_the_paths_they_share(pdeip, case):
+    """What the C++ drivers state once for several of them (csrc/pdeip_drivers.hip: the scale loop, the data-term front, the solver
+    dispatch, the entry checks), on paths no other case takes, against the Python drivers, bit for bit: a Vs-only a-priori field, a
+    scl_factor other than 0.75 through 1/scl_factor and as_diff, AD with Vs under 'flow' diffusion, the disparity driver's second
+    'rgb' term under the red-black point solver, HS with its default iter at scl_factor 0.6 in exact order, and param.scales beyond
+    the scale at which the frame stops shrinking (ceil(12 * 0.92) is 12, above the disparity driver's 10): the pyramid goes on to
+    param.scales with scales of one size, as pyramid.build_dev does -- only the TV drivers end there."""
+    D = drv()
+    if case.startswith("disp"):
+        left, right = _stereo_pair()
+        L3, R3 = np.stack([left] * 3, axis=2).astype(np.float32), np.stack([right] * 3, axis=2).astype(np.float32)
+        fst, snd, kw = {"disp_scl06": ("grad", "gradmag", dict(scl_factor=0.6, scales=4, Us=np.full(left.shape, -2.5))),
+                        "disp_rgb_rgb_point_rb": ("rgb", "rgb", dict(mode=pdeip.MODE_RED_BLACK, solver=1, omega=1.5, scales=3)),
+                        "disp_scales_past_shrinking": ("rgb", "none", dict(mode=pdeip.MODE_RED_BLACK, solver=1, omega=1.5, scl_factor=0.92, scales=60,
+                                                                          firstLoop=1, secondLoop=2))}[case]
+        want, got = D.DispEminND_llin_2D(L3, R3, fst, snd, **kw), D.capi_DispEminND_llin_2D(L3, R3, fst, snd, **kw)
+        assert pb.bit_equal(got, want), "%s: %s" % (case, pb.describe_mismatch(got, want))
+        return
+    I, Ut, Vt = _yosemite255()
+    if case == "hs_default_iter_scl06":
+        want, got = D.FlowEminHS_elin_2D_v10(I, 1, scl_factor=0.6), D.capi_FlowEminHS_elin_2D_v10(I, 1, scl_factor=0.6)
+    elif case == "ad_vs_flow_diffusion":
+        kw = dict(diffusion="flow", scales=3, firstLoop=2, Vs=Vt.astype(np.float64), gammaS=0.02)
+        want, got = D.FlowEminAD_llin_2D_v10(I, 1, "rgb", "none", **kw), D.capi_FlowEminAD_llin_2D_v10(I, 1, "rgb", "none", **kw)
+    else:
+        fst, snd, kw = {"nd_vs_only": ("rgb", "none", dict(scales=4, firstLoop=2, Vs=np.where(Ut > 0, np.nan, Vt).astype(np.float64), gammaS=0.02)),
+                        "nd_scl06": ("grad", "gradmag", dict(scl_factor=0.6, scales=4, Us=Ut.astype(np.float64)))}[case]
+        want, got = D.FlowEminND_llin_2D_v10(I, 1, fst, snd, **kw), D.capi_FlowEminND_llin_2D_v10(I, 1, fst, snd, **kw)
+    for g, w in zip(got, want):
+        assert pb.bit_equal(g, w), "%s: %s" % (case, pb.describe_mismatch(g, w))
+
+
 def test_resident_tv_drivers_equal_the_python_drivers(pdeip):
     """pdeip_tvdenoise8 / pdeip_tvdenoise4 (runme.m:143-144 as one C-ABI call each) against the Python drivers, bit for bit:
     grey and three-frame images, both orderings and solvers, non-default pyramids and loop counts; and through the MEX stubs."""
