@@ -8,7 +8,8 @@
 //   col = (i >= 1 && g == 0) ? clamp(PHI) : clamp(0.0f + xc)
 //   out = (j >= 1 && g == 0) ? clamp(PHI) : clamp(col + xr)
 // (the first element of a line is never tested; 0.0f + xc because the output array starts as zeros).  So the step is two
-// launches: k_cv_lines runs the column lanes and the row lanes side by side in one grid, k_cv_combine applies the rules.
+// launches: k_cv_lines runs the column lanes and the row lanes side by side in one grid (the line solve and that grid:
+// pdeip_thomas.hpp), k_cv_combine applies the rules.
 //
 // clamp is the reference's pair of ifs, not fminf/fmaxf: a NaN passes through.
 #pragma once
@@ -34,79 +35,27 @@ __device__ __forceinline__ Coef cv_coef(const float *__restrict__ PHI, const flo
     return r;
 }
 
-// One Thomas solve of a line: the forward sweep of aos_line (LS_CH elements' coefficients fetched ahead of the chain), then
-// x[n-1] = dp[n-1], x[k] = dp[k] - cp[k]*x[k+1] written to x at the line's own positions (base + k*stride).
+// One Thomas solve of a line L, x written at the line's own positions (base + k*stride).
 __device__ __forceinline__ void cv_line(const float *__restrict__ PHI, const float *__restrict__ D, const float *__restrict__ DH,
                                         const float *__restrict__ G, float *__restrict__ x, float *__restrict__ cp,
-                                        float *__restrict__ dp, size_t base, size_t stride, size_t sbase, size_t sstride, int n,
-                                        float tau, float nu)
+                                        float *__restrict__ dp, Line L, float tau, float nu)
 {
-    Coef c0 = cv_coef(PHI, D, DH, G, base, stride, 0, n, tau, nu);
-    float cpv = c0.c / c0.b;
-    float dpv = c0.d / c0.b;
-    cp[sbase] = cpv;
-    dp[sbase] = dpv;
-    for (int k0 = 1; k0 <= n - 2; k0 += LS_CH) {
-        Coef c[LS_CH];
-#pragma unroll
-        for (int u = 0; u < LS_CH; ++u) c[u] = cv_coef(PHI, D, DH, G, base, stride, min(k0 + u, n - 2), n, tau, nu);
-#pragma unroll
-        for (int u = 0; u < LS_CH; ++u) {
-            const int k = k0 + u;
-            if (k <= n - 2) {
-                const float div = 1.0f / (c[u].b - cpv * c[u].a);
-                cpv = c[u].c * div;
-                dpv = (c[u].d - dpv * c[u].a) * div;
-                cp[sbase + (size_t)k * sstride] = cpv;
-                dp[sbase + (size_t)k * sstride] = dpv;
-            }
-        }
-    }
-    {
-        const Coef cl = cv_coef(PHI, D, DH, G, base, stride, n - 1, n, tau, nu);
-        dpv = (cl.d - dpv * cl.a) / (cl.b - cpv * cl.a); // the last element divides (:247, :368)
-    }
-    float x1 = dpv;
-    x[base + (size_t)(n - 1) * stride] = x1;
-    for (int k0 = n - 2; k0 >= 0; k0 -= LS_CH) {
-        float cpk[LS_CH], dpk[LS_CH];
-#pragma unroll
-        for (int u = 0; u < LS_CH; ++u) {
-            const int k = max(k0 - u, 0);
-            cpk[u] = cp[sbase + (size_t)k * sstride];
-            dpk[u] = dp[sbase + (size_t)k * sstride];
-        }
-#pragma unroll
-        for (int u = 0; u < LS_CH; ++u) {
-            const int k = k0 - u;
-            if (k >= 0) {
-                x1 = dpk[u] - cpk[u] * x1;
-                x[base + (size_t)k * stride] = x1;
-            }
-        }
-    }
+    auto coef_at = [&](int k) __attribute__((always_inline)) { return cv_coef(PHI, D, DH, G, L.base, L.stride, k, L.n, tau, nu); };
+    auto store = [&](int k, float v) __attribute__((always_inline)) { x[L.base + (size_t)k * L.stride] = v; };
+    thomas::back_plain(cp, dp, L.sbase, L.sstride, L.n, thomas::forward(coef_at, cp, dp, L.sbase, L.sstride, L.n), store);
 }
 
-// Both line kinds in one grid, one wave per block.  blockIdx.y = frame; blockIdx.x < row_blocks: row lanes (row i, the longer
-// chains at landscape shapes, dispatched first), else column lanes (column j).  Row lanes: cp/dp share the image layout.
-// Column lanes: cp/dp transposed (element i of column j at i*ncols + j) so that a wave's scratch traffic is one contiguous run.
-// xc / xr are written in the image layout.
-__global__ void __launch_bounds__(LS_BLOCK) k_cv_lines(const float *__restrict__ PHI, const float *__restrict__ D,
-                                                       const float *__restrict__ DH, const float *__restrict__ G,
-                                                       float *__restrict__ xc, float *__restrict__ xr, float *__restrict__ cpc,
-                                                       float *__restrict__ dpc, float *__restrict__ cpr, float *__restrict__ dpr,
-                                                       int nrows, int ncols, int row_blocks, float tau, float nu)
+// Both line kinds in one grid (thomas::lane_of), blockIdx.y = frame.  xc / xr are written in the image layout.
+__global__ void __launch_bounds__(BLOCK) k_cv_lines(const float *__restrict__ PHI, const float *__restrict__ D,
+                                                    const float *__restrict__ DH, const float *__restrict__ G,
+                                                    float *__restrict__ xc, float *__restrict__ xr, float *__restrict__ cpc,
+                                                    float *__restrict__ dpc, float *__restrict__ cpr, float *__restrict__ dpr,
+                                                    int nrows, int ncols, int row_blocks, float tau, float nu)
 {
     const size_t fo = (size_t)blockIdx.y * nrows * ncols;
-    if ((int)blockIdx.x < row_blocks) {
-        const int i = blockIdx.x * LS_BLOCK + threadIdx.x;
-        if (i >= nrows) return;
-        cv_line(PHI, D, DH, G, xr, cpr, dpr, fo + i, (size_t)nrows, fo + i, (size_t)nrows, ncols, tau, nu);
-    } else {
-        const int j = ((int)blockIdx.x - row_blocks) * LS_BLOCK + threadIdx.x;
-        if (j >= ncols) return;
-        cv_line(PHI, D, DH, G, xc, cpc, dpc, fo + (size_t)j * nrows, 1, fo + j, (size_t)ncols, nrows, tau, nu);
-    }
+    const thomas::Lane l = thomas::lane_of(blockIdx.x, row_blocks, nrows, ncols);
+    if (l.kind == thomas::ROW) cv_line(PHI, D, DH, G, xr, cpr, dpr, thomas::row_line(fo, l.idx, nrows, ncols), tau, nu);
+    else if (l.kind == thomas::COL) cv_line(PHI, D, DH, G, xc, cpc, dpc, thomas::col_line(fo, l.idx, nrows, ncols), tau, nu);
 }
 
 // The two passes' output rules, pixel (i, j) of frame blockIdx.z.

@@ -1,7 +1,7 @@
 // pdeip_diffusion.hip -- libpdeip.so: Iout = Diffusion4_v10(I_in, 'alpha', alpha, 'outer_iter', K) (matlab/diffusion/
 // Diffusion4_v10.m) as one resident call, pdeip_diffusion4 / pdeip_diffusion4_dev, before the driver's uint8 cast.
 //
-// Kernels: csrc/pdeip_diffusion.hpp.  The weights are k_diffweights6 (csrc/pdeip_pointwise.hpp, DdiffWeights) launched here
+// Kernels: csrc/pdeip_diffusion.hpp (the line solve and its grid: csrc/pdeip_thomas.hpp).  The weights are k_diffweights6 (csrc/pdeip_pointwise.hpp, DdiffWeights) launched here
 // directly: its entry point pdeip_diffweights6_dev keeps the gateway's 3x3 minimum, and this driver accepts 2-element lines.
 // The maximum over the channels is the .m's max(w, [], 3), which omits a NaN of any channel (k_diffweights6<true>); the
 // gateway's C keeps a NaN of its first frame (<false>, pdeip_diffweights6_dev).
@@ -71,15 +71,14 @@ extern "C" int pdeip_diffusion4_dev(void *stream, const float *Iin, int nrows, i
         float *ws = nullptr;
         RC(ws_get(WS_DRIVER, (4 * pn + 6 * pc) * sizeof(float), &ws));
         float *wW = ws, *wN = wW + pn, *wE = wN + pn, *wS = wE + pn;
-        float *xc = wS + pn, *xr = xc + pc, *cpc = xr + pc, *dpc = cpc + pc, *cpr = dpc + pc, *dpr = cpr + pc;
-        const int rb = (nrows + D4_BLOCK - 1) / D4_BLOCK, cb = (ncols + D4_BLOCK - 1) / D4_BLOCK;
-        const dim3 lines((unsigned)(rb + cb), (unsigned)channels), sum((unsigned)((nc + 255) / 256));
+        const thomas::Planes w = thomas::carve_planes(wS + pn, pc);
+        const dim3 lines = thomas::lines_grid(nrows, ncols, channels), sum((unsigned)((nc + 255) / 256));
         for (int it = 0; it < iters; it++) {
             hipLaunchKernelGGL(k_diffweights6<true>, pixel_grid(nrows, ncols, 1), dim3(256), 0, s, wW, wN, wE, wS, Iout, nrows, ncols,
                                channels, 0.00001f);
-            hipLaunchKernelGGL(k_diff4_lines, lines, dim3(D4_BLOCK), 0, s, Iout, wW, wN, wE, wS, xc, xr, cpc, dpc, cpr, dpr, nrows,
-                               ncols, rb, alpha);
-            hipLaunchKernelGGL(k_diff4_combine, sum, dim3(256), 0, s, xc, xr, Iout, nc);
+            hipLaunchKernelGGL(k_diff4_lines, lines, dim3(thomas::BLOCK), 0, s, Iout, wW, wN, wE, wS, w.xc, w.xr, w.cpc, w.dpc, w.cpr,
+                               w.dpr, nrows, ncols, thomas::line_blocks(nrows), alpha);
+            hipLaunchKernelGGL(k_diff4_combine, sum, dim3(256), 0, s, w.xc, w.xr, Iout, nc);
             HIPCHK(hipGetLastError());
             launches += 3;
         }

@@ -7,8 +7,9 @@
 //   PHIout = GAC_v10a / GAC_v10b(Iin, PHIin, ...)             matlab/active_contour/GAC_v10{a,b}.m      pdeip_gac(_dev)
 //   sort(x)(k) and [Igrad, lambda, g] of those drivers: the stages before their loop                     pdeip_select_kth_dev, pdeip_gac_stopping_dev
 //
-// Kernels: csrc/pdeip_levelset.hpp, csrc/pdeip_cv.hpp.  AOS has one order, so pdeip_set_mode does not apply.  Multi-frame inputs are planes
-// solved independently, as in the reference.  Lines of any length are accepted (the reference stops at MAX_BUF_SIZE = 2048).
+// Kernels: csrc/pdeip_levelset.hpp, csrc/pdeip_cv.hpp; their line solve and its grid: csrc/pdeip_thomas.hpp.  AOS has one order,
+// so pdeip_set_mode does not apply.  Multi-frame inputs are planes solved independently, as in the reference.  Lines of any length
+// are accepted (the reference stops at MAX_BUF_SIZE = 2048).
 //
 // Build (build.py): hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -c, one object per translation unit.
 #include "pdeip_ctx.hpp"
@@ -79,10 +80,10 @@ extern "C" int pdeip_ac_solver_dev(void *stream, const float *PHI, const float *
     float *cp = ws, *dp = ws + pad4(nf), *sum = ws + 2 * pad4(nf);
     hipStream_t s = static_cast<hipStream_t>(stream);
     // column pass -> PHI_out (AC_TDMA_column4), row pass -> sum (AC_TDMA_row4), one re-initialisation step -> PHI_out (:178)
-    hipLaunchKernelGGL(k_aos_col, dim3((unsigned)((ncols + LS_BLOCK - 1) / LS_BLOCK), (unsigned)nframes), dim3(LS_BLOCK), 0, s,
+    hipLaunchKernelGGL(k_aos_col, dim3((unsigned)thomas::line_blocks(ncols), (unsigned)nframes), dim3(thomas::BLOCK), 0, s,
                        PHI, D, GradNorm, Diff, PHI_out, cp, dp, nrows, ncols, tau, nu);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_aos_row, dim3((unsigned)((nrows + LS_BLOCK - 1) / LS_BLOCK), (unsigned)nframes), dim3(LS_BLOCK), 0, s,
+    hipLaunchKernelGGL(k_aos_row, dim3((unsigned)thomas::line_blocks(nrows), (unsigned)nframes), dim3(thomas::BLOCK), 0, s,
                        PHI, D, GradNorm, Diff, PHI_out, sum, cp, dp, nrows, ncols, tau, nu);
     HIPCHK(hipGetLastError());
     tls.last_launches += 2;
@@ -319,14 +320,14 @@ extern "C" int pdeip_cv_solver_dev(void *stream, const float *PHI, const float *
     const size_t p = pad4((size_t)nrows * ncols * nframes);
     float *ws = nullptr;
     RC(ws_get(WS_LS, p * 6 * sizeof(float), &ws));
-    float *cpc = ws, *dpc = ws + p, *cpr = ws + 2 * p, *dpr = ws + 3 * p, *xc = ws + 4 * p, *xr = ws + 5 * p;
+    const thomas::Planes w = thomas::carve_planes(ws, p);
     hipStream_t s = static_cast<hipStream_t>(stream);
     // column lanes and row lanes in one grid (their chains do not depend on each other), then the output rules
-    const int rb = (nrows + LS_BLOCK - 1) / LS_BLOCK, cb = (ncols + LS_BLOCK - 1) / LS_BLOCK;
-    hipLaunchKernelGGL(k_cv_lines, dim3((unsigned)(rb + cb), (unsigned)nframes), dim3(LS_BLOCK), 0, s, PHI, D, DH, GradNorm, xc, xr,
-                       cpc, dpc, cpr, dpr, nrows, ncols, rb, tau, nu);
+    hipLaunchKernelGGL(k_cv_lines, thomas::lines_grid(nrows, ncols, nframes), dim3(thomas::BLOCK), 0, s, PHI, D, DH, GradNorm, w.xc,
+                       w.xr, w.cpc, w.dpc, w.cpr, w.dpr, nrows, ncols, thomas::line_blocks(nrows), tau, nu);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_cv_combine, pixel_grid(nrows, ncols, nframes), dim3(256), 0, s, PHI, GradNorm, xc, xr, PHI_out, nrows, ncols);
+    hipLaunchKernelGGL(k_cv_combine, pixel_grid(nrows, ncols, nframes), dim3(256), 0, s, PHI, GradNorm, w.xc, w.xr, PHI_out, nrows,
+                       ncols);
     HIPCHK(hipGetLastError());
     tls.last_launches = 2;
     return PDEIP_OK;

@@ -2,11 +2,8 @@
 // library/levelsetSolvers.c:145-181) and the re-initialisation step of reinit() (:969-1118).
 //
 // AOS.  Every line (column or row of one frame) is one tridiagonal Thomas solve, independent of every other line: one lane
-// per line, the recurrence serial inside the lane so that every operation keeps the reference's order.  The coefficients
-// a, b, c, d of LS_CH consecutive elements are computed before the chain runs through them, so only b - cp*a, the
-// reciprocal and the two multiplies sit on the dependency chain.  cp/dp live in a global scratch buffer laid out so that
-// the 64 lanes of a wave touch 64 consecutive floats at every step; the reference's 2048-element line limit
-// (MAX_BUF_SIZE) does not apply.
+// per line, forward sweep, scratch layout and line geometry from pdeip_thomas.hpp; the back-substitution is this step's own.
+// The reference's 2048-element line limit (MAX_BUF_SIZE) does not apply.
 //
 // Both passes write   out = x + carry   where `carry` is 0 for the column pass (the output array starts as zeros,
 // :751-768) and the column result for the row pass (:853-870).  The passes treat Diff == 0 differently, both reproduced:
@@ -19,17 +16,15 @@
 // function is this library's contract: S = PHI * (1/sqrtf(PHI^2 + sqrtf((PHIx^2 + PHIy^2) + FLT_EPSILON)))
 // -- the SSE path's operation order with a correctly rounded reciprocal square root instead of rsqrtps.
 #pragma once
-#include <hip/hip_runtime.h>
+#include "pdeip_thomas.hpp"
 
 namespace pdeip {
 namespace ls {
 
-constexpr int LS_CH = 8;       // elements whose coefficients are fetched ahead of the chain
-constexpr int LS_BLOCK = 64;   // one wave per block: the few lines of a frame spread over as many CUs as possible
-
-struct Coef {
-    float a, b, c, d;
-};
+using thomas::BLOCK;
+using thomas::CH;
+using thomas::Coef;
+using thomas::Line;
 
 // Harmonic diffusivity between `pos` and its neighbour `q` (:705-706): a non-positive or NaN sum gives 0.
 __device__ __forceinline__ float harm(const float *__restrict__ Diff, const float *__restrict__ GN, size_t pos, size_t q, float tau)
@@ -65,48 +60,24 @@ __device__ __forceinline__ Coef aos_coef(const float *__restrict__ PHI, const fl
     return r;
 }
 
-// One Thomas solve of a line.  Line elements at base + k*stride; cp/dp of element k at sbase + k*sstride.  ROW selects the
-// row pass's Diff == 0 rule and its carry (the column values already in `out`); the column pass has carry 0.
+// One Thomas solve of a line L: thomas::forward (:700-742), then the AOS back-substitution.  ROW selects the row pass's
+// Diff == 0 rule and its carry (the column values already in `out`); the column pass has carry 0.
 template <bool ROW>
 __device__ __forceinline__ void aos_line(const float *__restrict__ PHI, const float *__restrict__ D, const float *__restrict__ GN,
                                          const float *__restrict__ Diff, const float *__restrict__ col, float *__restrict__ out,
-                                         float *__restrict__ cp, float *__restrict__ dp, size_t base, size_t stride, size_t sbase,
-                                         size_t sstride, int n, float tau, float nu)
+                                         float *__restrict__ cp, float *__restrict__ dp, Line L, float tau, float nu)
 {
-    // ---- forward sweep (:700-742) ----
-    Coef c0 = aos_coef(PHI, D, GN, Diff, base, stride, 0, n, tau, nu);
-    float cpv = c0.c / c0.b;
-    float dpv = c0.d / c0.b;
-    cp[sbase] = cpv;
-    dp[sbase] = dpv;
-    for (int k0 = 1; k0 <= n - 2; k0 += LS_CH) {
-        Coef c[LS_CH];
-#pragma unroll
-        for (int u = 0; u < LS_CH; ++u) c[u] = aos_coef(PHI, D, GN, Diff, base, stride, min(k0 + u, n - 2), n, tau, nu);
-#pragma unroll
-        for (int u = 0; u < LS_CH; ++u) {
-            const int k = k0 + u;
-            if (k <= n - 2) {
-                const float div = 1.0f / (c[u].b - cpv * c[u].a);
-                cpv = c[u].c * div;
-                dpv = (c[u].d - dpv * c[u].a) * div;
-                cp[sbase + (size_t)k * sstride] = cpv;
-                dp[sbase + (size_t)k * sstride] = dpv;
-            }
-        }
-    }
-    {
-        const Coef cl = aos_coef(PHI, D, GN, Diff, base, stride, n - 1, n, tau, nu);
-        dpv = (cl.d - dpv * cl.a) / (cl.b - cpv * cl.a); // the last element divides (:735)
-    }
+    const size_t base = L.base, stride = L.stride, sbase = L.sbase, sstride = L.sstride;
+    const int n = L.n;
+    auto coef_at = [&](int k) __attribute__((always_inline)) { return aos_coef(PHI, D, GN, Diff, base, stride, k, n, tau, nu); };
     // ---- back-substitution (:737-768 / :850-876) ----
     // x1/t1: x and carry of element k+1 (the carry of the last element is its column value; it is never tested)
-    float x1 = dpv;
+    float x1 = thomas::forward(coef_at, cp, dp, sbase, sstride, n);
     float t1 = ROW ? col[base + (size_t)(n - 1) * stride] : 0.0f;
-    for (int k0 = n - 2; k0 >= 0; k0 -= LS_CH) {
-        float cpk[LS_CH], dpk[LS_CH], dfk[LS_CH], phk[LS_CH], clk[LS_CH];
+    for (int k0 = n - 2; k0 >= 0; k0 -= CH) {
+        float cpk[CH], dpk[CH], dfk[CH], phk[CH], clk[CH];
 #pragma unroll
-        for (int u = 0; u < LS_CH; ++u) {
+        for (int u = 0; u < CH; ++u) {
             const int k = max(k0 - u, 0);
             const size_t pos = base + (size_t)k * stride;
             cpk[u] = cp[sbase + (size_t)k * sstride];
@@ -116,7 +87,7 @@ __device__ __forceinline__ void aos_line(const float *__restrict__ PHI, const fl
             clk[u] = ROW ? col[pos] : 0.0f;
         }
 #pragma unroll
-        for (int u = 0; u < LS_CH; ++u) {
+        for (int u = 0; u < CH; ++u) {
             const int k = k0 - u;
             if (k >= 0) {
                 const size_t pos = base + (size_t)k * stride;
@@ -139,32 +110,31 @@ __device__ __forceinline__ void aos_line(const float *__restrict__ PHI, const fl
     out[base] = x1 + t1;
 }
 
-// Column pass: lane = column j of frame blockIdx.y.  Lines are contiguous; cp/dp are stored transposed (element i of column
-// j at i*ncols + j) so that the scratch traffic of a wave is one contiguous run per step.
-__global__ void __launch_bounds__(LS_BLOCK) k_aos_col(const float *__restrict__ PHI, const float *__restrict__ D,
-                                                      const float *__restrict__ GN, const float *__restrict__ Diff,
-                                                      float *__restrict__ out, float *__restrict__ cp, float *__restrict__ dp,
-                                                      int nrows, int ncols, float tau, float nu)
+// Column pass: lane = column j of frame blockIdx.y (thomas::col_line).
+__global__ void __launch_bounds__(BLOCK) k_aos_col(const float *__restrict__ PHI, const float *__restrict__ D,
+                                                   const float *__restrict__ GN, const float *__restrict__ Diff,
+                                                   float *__restrict__ out, float *__restrict__ cp, float *__restrict__ dp,
+                                                   int nrows, int ncols, float tau, float nu)
 {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= ncols) return;
     const size_t fo = (size_t)blockIdx.y * nrows * ncols;
-    aos_line<false>(PHI, D, GN, Diff, nullptr, out, cp, dp, fo + (size_t)j * nrows, 1, fo + j, (size_t)ncols, nrows, tau, nu);
+    aos_line<false>(PHI, D, GN, Diff, nullptr, out, cp, dp, thomas::col_line(fo, j, nrows, ncols), tau, nu);
 }
 
-// Row pass: lane = row i of frame blockIdx.y.  Lines are strided by nrows, so a wave's loads are coalesced as they are;
-// cp/dp share the image layout.  `col` is the column pass's output (read), `out` the sum (written); they may not alias
-// across lanes, and each lane only touches its own row of both.
-__global__ void __launch_bounds__(LS_BLOCK) k_aos_row(const float *__restrict__ PHI, const float *__restrict__ D,
-                                                      const float *__restrict__ GN, const float *__restrict__ Diff,
-                                                      const float *__restrict__ col, float *__restrict__ out,
-                                                      float *__restrict__ cp, float *__restrict__ dp, int nrows, int ncols,
-                                                      float tau, float nu)
+// Row pass: lane = row i of frame blockIdx.y (thomas::row_line); a launch of its own because it reads the column pass.  `col`
+// is the column pass's output (read), `out` the sum (written); they may not alias across lanes, and each lane only touches its
+// own row of both.
+__global__ void __launch_bounds__(BLOCK) k_aos_row(const float *__restrict__ PHI, const float *__restrict__ D,
+                                                   const float *__restrict__ GN, const float *__restrict__ Diff,
+                                                   const float *__restrict__ col, float *__restrict__ out,
+                                                   float *__restrict__ cp, float *__restrict__ dp, int nrows, int ncols,
+                                                   float tau, float nu)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nrows) return;
     const size_t fo = (size_t)blockIdx.y * nrows * ncols;
-    aos_line<true>(PHI, D, GN, Diff, col, out, cp, dp, fo + i, (size_t)nrows, fo + i, (size_t)nrows, ncols, tau, nu);
+    aos_line<true>(PHI, D, GN, Diff, col, out, cp, dp, thomas::row_line(fo, i, nrows, ncols), tau, nu);
 }
 
 __device__ __forceinline__ float maxP2(float A) { return (A > 0.0f) ? (A * A) : 0.0f; } // :41-43
