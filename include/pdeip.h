@@ -1251,6 +1251,84 @@ int pdeip_flow_interpolate(const float *I0, const float *I1, int channels, const
                            const float *Vb, int nrows, int ncols, double t, const pdeip_interp_params *prm, float *It_out,
                            float *Ut_out, float *Vt_out, float *source_out);
 
+/* ---- exact Euclidean distance transform: bwdist, signed distance, nearest fill (csrc/pdeip_edt.hip) ----------------------------------
+ *
+ * This library's own definitions (the reference has no such function; MATLAB's bwdist is the model); tests/edt_ref.py restates them.
+ * Planes are column-major float32 [nrows x ncols x frames]; each frame is transformed on its own.
+ *
+ * pdeip_edt / pdeip_edt_dev.  A pixel is a FEATURE according to `mode`:
+ *   PDEIP_EDT_POSITIVE   A > 0    the predicate of bwdist(A > 0) and of pdeip_bwlabel; NaN is not a feature
+ *   PDEIP_EDT_NONNEG     A >= 0   the library's "inside" of a level set; -0.0 is inside, NaN is not
+ *   PDEIP_EDT_NOT_NAN    A == A   the known pixels of a sparse map; +-Inf is known, as in pdeip_tv_inpaint4
+ *   PDEIP_EDT_*_NOT      the complement of each (a NaN is then a feature of the first two)
+ * Per pixel (every output may be NULL, but not all three):
+ *   d2_out    int32: the exact squared Euclidean distance, in pixels, to the nearest feature
+ *   idx_out   int32: the 0-based column-major linear index j nrows + i, within the frame, of that feature
+ *   dist_out  float32: (float)sqrt((double)d2), both operations correctly rounded
+ * A frame without a feature, or a pixel beyond max_dist: d2 = INT32_MAX, idx = -1, dist = +Inf.
+ * Ties: among equidistant features the one with the LOWEST LINEAR INDEX wins -- the smallest column, then the smallest row.  The
+ * result therefore does not depend on scheduling and is reproducible to the bit.
+ * max_dist <= 0: unbounded.  max_dist = R > 0: features farther than R pixels along either axis are not looked at, and a pixel whose
+ * nearest feature has d2 > R^2 reports "none"; this bounds the work per pixel by 2 R + 1 columns.
+ * The transform is separable and all integer: a column pass finds every pixel's nearest feature within its own column (the upper of
+ * two equidistant ones), a row pass minimises (d^2 + g^2, idx) over the columns j -+ d outward and stops once d^2 exceeds the best
+ * squared distance.  Its work per pixel is proportional to the distance found, so it depends on the content: near one pass over the
+ * plane for masks and sparse maps, O(ncols) per pixel for a single feature in a large frame.
+ * _dev: device pointers, launches on `stream`, nothing read back, graph-capturable once an eager call has created the workspace (one
+ * int32 per element); 2 launches (columns, rows), whatever the data (pdeip_last_launch_count()).  A is never written; planes may start
+ * at any 4-byte offset.
+ * Refused with PDEIP_ERR_ARG before any HIP call: NULL A, all outputs NULL, frames < 1, a side < 1, an unknown mode, more than 2^31-1
+ * elements; PDEIP_ERR_UNSUPPORTED: a side above 32767 (d2 must fit an int32).  A 1 x 1 plane is accepted.
+ *
+ * pdeip_bwdist / pdeip_bwdist_dev: [D, IDX] = bwdist(BW) with the Euclidean metric: the transform in mode PDEIP_EDT_POSITIVE, unbounded;
+ * D_out = dist, idx_out = the 0-based idx (either may be NULL, not both).  2 launches.  Refusals as above.
+ *
+ * pdeip_signed_distance / pdeip_signed_distance_dev: the signed distance of the level set whose inside is A >= 0,
+ *   out = dist_to_outside - 0.5   on an inside pixel    (dist of the transform in mode PDEIP_EDT_NONNEG_NOT)
+ *   out = -(dist_to_inside - 0.5) on an outside pixel   (dist of the transform in mode PDEIP_EDT_NONNEG)
+ * the subtraction a single float32 operation.  The interface lies half-way between an inside pixel and its outside neighbour: |out| is
+ * never below 0.5 and the sign of out is the input's side.  A plane that is all inside is +Inf, one that is all outside -Inf.  With
+ * max_dist = R > 0 a distance "none" counts as (float)(R + 1), so values beyond the band saturate at +-(R + 0.5): such a plane is
+ * what pdeip_ac_solver can take.  5 launches (two transforms, k_sdf_combine); workspace: three planes.  out may be A.  Refused as
+ * above, and: NULL out.
+ *
+ * pdeip_nearest_fill / pdeip_nearest_fill_dev: per frame the transform in mode PDEIP_EDT_NOT_NAN, then one gather launch.  A known
+ * pixel keeps its own bits (-0.0 included, as in pdeip_inpaint_merge_dev); a hole takes the bits of D[idx]; a hole without a source
+ * (an empty frame, or none within max_dist) stays NaN.  filled_out (NULL allowed): 1 on the holes that were filled, 0 elsewhere;
+ * dist_out (NULL allowed): the transform's dist.  3 launches; workspace: two planes.  out may be D.  Refused as above, and: NULL out,
+ * filled_out or dist_out equal to another plane of the call.
+ * This is the cheapest well-defined fill, NOT a substitute for pdeip_tv_inpaint4 on occlusion bands: the nearest neighbour of an
+ * occlusion band is the foreground (3.45 px RMS on the scene of tests/inpaint_cases.py, against 3.11 for the mean and 1.20 for TV).
+ *
+ * pdeip_flow_interpolate_nearest / _dev: pdeip_flow_interpolate with step 3 replaced: one transform (PDEIP_EDT_NOT_NAN, max_dist) of
+ * the splatted Ut's holes -- the splat gives Ut and Vt the same holes -- and one gather of both planes through its index; a hole
+ * without a source becomes 0, so a field without any finite source gives the zero-flow blend.  Steps 1, 2 and 4 are the same calls.
+ * prm->fill must be NULL (PDEIP_ERR_ARG otherwise); the other refusals are pdeip_flow_interpolate's, and a side above 32767.
+ * _dev launches: [2 with Ub, Vb] + 3 (splat) + 2 (transform) + 1 (gather) + 1 (blend), plus one copy per Ut_out / Vt_out given,
+ * whatever the data; graph-capturable once an eager call has created the workspaces. */
+#define PDEIP_EDT_POSITIVE 0
+#define PDEIP_EDT_NONNEG 1
+#define PDEIP_EDT_NOT_NAN 2
+#define PDEIP_EDT_POSITIVE_NOT 4
+#define PDEIP_EDT_NONNEG_NOT 5
+#define PDEIP_EDT_NOT_NAN_NOT 6
+int pdeip_edt_dev(void *stream, const float *A, int nrows, int ncols, int frames, int mode, int max_dist, int *d2_out, int *idx_out,
+                  float *dist_out);
+int pdeip_edt(const float *A, int nrows, int ncols, int frames, int mode, int max_dist, int *d2_out, int *idx_out, float *dist_out);
+int pdeip_bwdist_dev(void *stream, const float *BW, int nrows, int ncols, int frames, float *D_out, int *idx_out);
+int pdeip_bwdist(const float *BW, int nrows, int ncols, int frames, float *D_out, int *idx_out);
+int pdeip_signed_distance_dev(void *stream, const float *A, int nrows, int ncols, int frames, int max_dist, float *out);
+int pdeip_signed_distance(const float *A, int nrows, int ncols, int frames, int max_dist, float *out);
+int pdeip_nearest_fill_dev(void *stream, const float *D, int nrows, int ncols, int frames, int max_dist, float *out, float *filled_out,
+                           float *dist_out);
+int pdeip_nearest_fill(const float *D, int nrows, int ncols, int frames, int max_dist, float *out, float *filled_out, float *dist_out);
+int pdeip_flow_interpolate_nearest_dev(void *stream, const float *I0, const float *I1, int channels, const float *Uf, const float *Vf,
+                                       const float *Ub, const float *Vb, int nrows, int ncols, double t, const pdeip_interp_params *prm,
+                                       int max_dist, float *It_out, float *Ut_out, float *Vt_out, float *source_out);
+int pdeip_flow_interpolate_nearest(const float *I0, const float *I1, int channels, const float *Uf, const float *Vf, const float *Ub,
+                                   const float *Vb, int nrows, int ncols, double t, const pdeip_interp_params *prm, int max_dist,
+                                   float *It_out, float *Ut_out, float *Vt_out, float *source_out);
+
 /* ---- structure-tensor anisotropic diffusion (csrc/pdeip_stensor.hip) --------------------------------------------------------
  * Weickert's edge-enhancing (EED) and coherence-enhancing (CED) diffusion, each semi-implicit step (I - tau A(u^k)) u^{k+1} = u^k
  * one PDEsolver8 solve by pdeip_pde_sor8_dev / pdeip_pde_alr8_dev.  Not in the reference toolbox; tests/stensor_ref.py restates

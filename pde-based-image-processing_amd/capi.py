@@ -19,6 +19,8 @@ MODE_EXACT_ORDER = 0
 MODE_RED_BLACK = 1
 SEG_SURFACE, SEG_GREEDY, SEG_INVERSE = 0, 1, 2  # PDEIP_SEG_*: the competition strategies
 MODE_LINE_SCAN = 2  # line relaxation in the reference's line order, a line's recurrences as parallel scans
+# PDEIP_EDT_*: which pixels are the features of the distance transform; + 4: the complement
+EDT_POSITIVE, EDT_NONNEG, EDT_NOT_NAN, EDT_POSITIVE_NOT, EDT_NONNEG_NOT, EDT_NOT_NAN_NOT = 0, 1, 2, 4, 5, 6
 
 _P = ctypes.c_void_p  # float* (host or device), passed as an address
 _I = ctypes.c_int
@@ -193,6 +195,17 @@ SIGNATURES = {
     "pdeip_interp_blend_dev": [_P, _P, _P, _I, _P, _P, _P, _P, _I, _I, ctypes.c_double, _P, _P],
     "pdeip_flow_interpolate_dev": [_P, _P, _P, _I, _P, _P, _P, _P, _I, _I, ctypes.c_double, _P, _P, _P, _P, _P],
     "pdeip_flow_interpolate": [_P, _P, _I, _P, _P, _P, _P, _I, _I, ctypes.c_double, _P, _P, _P, _P, _P],
+    # distance transform, signed distance, nearest fill (csrc/pdeip_edt.hip)
+    "pdeip_edt_dev": [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P],
+    "pdeip_edt": [_P, _I, _I, _I, _I, _I, _P, _P, _P],
+    "pdeip_bwdist_dev": [_P, _P, _I, _I, _I, _P, _P],
+    "pdeip_bwdist": [_P, _I, _I, _I, _P, _P],
+    "pdeip_signed_distance_dev": [_P, _P, _I, _I, _I, _I, _P],
+    "pdeip_signed_distance": [_P, _I, _I, _I, _I, _P],
+    "pdeip_nearest_fill_dev": [_P, _P, _I, _I, _I, _I, _P, _P, _P],
+    "pdeip_nearest_fill": [_P, _I, _I, _I, _I, _P, _P, _P],
+    "pdeip_flow_interpolate_nearest_dev": [_P, _P, _P, _I, _P, _P, _P, _P, _I, _I, ctypes.c_double, _P, _I, _P, _P, _P, _P],
+    "pdeip_flow_interpolate_nearest": [_P, _P, _I, _P, _P, _P, _P, _I, _I, ctypes.c_double, _P, _I, _P, _P, _P, _P],
     # structure-tensor anisotropic diffusion (csrc/pdeip_stensor.hip)
     "pdeip_gauss_taps": [ctypes.c_double, _P, _I, ctypes.POINTER(ctypes.c_int)],
     "pdeip_gauss": [_P, _I, _I, _I, ctypes.c_double, _P],

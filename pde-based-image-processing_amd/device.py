@@ -1148,11 +1148,21 @@ def interp_blend(I0, I1, Ut, Vt, t=0.5, M0=None, M1=None, It_out=None, source_ou
 
 
 def flow_interpolate(I0, I1, Uf, Vf, Ub=None, Vb=None, t=0.5, It_out=None, Ut_out=None, Vt_out=None, source_out=None, flow=True, source=True,
-                     mode=None, **param):
+                     mode=None, fill_with="tv", max_dist=0, **param):
     """The whole resident chain (pdeip_flow_interpolate_dev): the cross-checks of (Uf, Vf) against (Ub, Vb) if the backward flow is
     given, the splat to time t, the hole filling and the blend.  Returns (It, Ut, Vt, source): the frame at t like I0, the filled flow
     at t and the source plane (None with flow=False / source=False unless handed in).  mode: the ordering of the hole filling's solver
-    calls (None: the library's current mode); param: a, b, use_costs and tv_inpaint4's.  Nothing is read back."""
+    calls (None: the library's current mode); param: a, b, use_costs and tv_inpaint4's.  fill_with="nearest": the holes take the
+    nearest source's flow instead (pdeip_flow_interpolate_nearest_dev; max_dist > 0 fills only that far, the rest becomes 0); TV
+    parameters are then a ValueError.  Nothing is read back."""
+    if fill_with not in ("tv", "nearest"):
+        raise ValueError("flow_interpolate: fill_with must be 'tv' or 'nearest' (got %r)" % (fill_with,))
+    if fill_with == "nearest":
+        tv = sorted(k for k in param if k not in ("a", "b", "use_costs"))
+        if tv:
+            raise ValueError("flow_interpolate: fill_with='nearest' takes no TV inpainting parameters (got %s)" % tv)
+    elif max_dist:
+        raise ValueError("flow_interpolate: max_dist belongs to fill_with='nearest'")
     _flow_planes("flow_interpolate", Uf, Vf, Ub, Vb)
     if (Ub is None) != (Vb is None):
         raise capi.PdeipError(capi.PDEIP_ERR_ARG, "flow_interpolate: Ub and Vb must both be given or both be None")
@@ -1163,6 +1173,10 @@ def flow_interpolate(I0, I1, Uf, Vf, Ub=None, Vb=None, t=0.5, It_out=None, Ut_ou
     Vt_out = _out_plane(Uf, Vt_out, flow, "flow_interpolate: Vt_out")
     source_out = _out_plane(Uf, source_out, source, "flow_interpolate: source_out")
     prm = InterpParams.make(**param)
+    if fill_with == "nearest":
+        capi.call("pdeip_flow_interpolate_nearest_dev", _stream(), *_p(I0, I1), channels, *_p(Uf, Vf), _ptr(Ub), _ptr(Vb), nrows, ncols,
+                  float(t), ctypes.addressof(prm), int(max_dist), It_out.data_ptr(), _ptr(Ut_out), _ptr(Vt_out), _ptr(source_out))
+        return It_out, Ut_out, Vt_out, source_out
     old = capi.get_mode()
     if mode is not None:
         capi.set_mode(mode)
@@ -1173,3 +1187,73 @@ def flow_interpolate(I0, I1, Uf, Vf, Ub=None, Vb=None, t=0.5, It_out=None, Ut_ou
         if mode is not None:
             capi.set_mode(old)
     return It_out, Ut_out, Vt_out, source_out
+
+
+# ---- exact Euclidean distance transform, signed distance, nearest fill (csrc/pdeip_edt.hip) ----
+EDT_MODES = {"positive": capi.EDT_POSITIVE, "nonneg": capi.EDT_NONNEG, "not_nan": capi.EDT_NOT_NAN, "positive_not": capi.EDT_POSITIVE_NOT,
+             "nonneg_not": capi.EDT_NONNEG_NOT, "not_nan_not": capi.EDT_NOT_NAN_NOT}
+
+
+def _typed_plane(like, given, wanted, dtype, what):
+    if given is None and wanted:
+        given = torch.empty(like.shape, dtype=dtype, device=like.device)
+    if given is not None:
+        _chk_typed(given, dtype, like.numel(), what)
+    return given
+
+
+def edt(A, mode="positive", max_dist=0, d2_out=None, idx_out=None, dist_out=None, d2=True, idx=True, dist=True):
+    """The exact Euclidean distance transform of the resident plane A [(F,) ncols, nrows] (pdeip_edt_dev), every frame on its own.
+    mode: which pixels are features -- 'positive' A > 0, 'nonneg' A >= 0, 'not_nan', each with a '_not' twin for the complement (or a
+    PDEIP_EDT_* number).  Returns (d2, idx, dist): int32 squared distance, int32 0-based column-major index of the nearest feature
+    within its frame (ties: the lowest index), float32 distance; INT32_MAX / -1 / +Inf where there is none (none at all, or none
+    within max_dist > 0).  An output is None with d2 / idx / dist False unless handed in.  Nothing is read back."""
+    _chk(A)
+    if isinstance(mode, str) and mode not in EDT_MODES:
+        raise capi.PdeipError(capi.PDEIP_ERR_ARG, "edt: unknown mode %r (one of %s)" % (mode, sorted(EDT_MODES)))
+    nrows, ncols, F = _dims(A)
+    d2_out = _typed_plane(A, d2_out, d2, torch.int32, "edt: d2_out")
+    idx_out = _typed_plane(A, idx_out, idx, torch.int32, "edt: idx_out")
+    dist_out = _typed_plane(A, dist_out, dist, torch.float32, "edt: dist_out")
+    capi.call("pdeip_edt_dev", _stream(), A.data_ptr(), nrows, ncols, F, int(EDT_MODES.get(mode, mode)), int(max_dist), _ptr(d2_out),
+              _ptr(idx_out), _ptr(dist_out))
+    return d2_out, idx_out, dist_out
+
+
+def bwdist(BW, D_out=None, idx_out=None, idx=True):
+    """[D, IDX] = bwdist(BW > 0), Euclidean (pdeip_bwdist_dev): BW float32 [(F,) ncols, nrows].  Returns (D, IDX): float32 distance to
+    the nearest positive pixel and its 0-based index (int32; -1 and +Inf in a frame without one; IDX None with idx=False unless handed
+    in).  Nothing is read back."""
+    _chk(BW)
+    nrows, ncols, F = _dims(BW)
+    D_out = _typed_plane(BW, D_out, True, torch.float32, "bwdist: D_out")
+    idx_out = _typed_plane(BW, idx_out, idx, torch.int32, "bwdist: idx_out")
+    capi.call("pdeip_bwdist_dev", _stream(), BW.data_ptr(), nrows, ncols, F, D_out.data_ptr(), _ptr(idx_out))
+    return D_out, idx_out
+
+
+def signed_distance(A, max_dist=0, out=None):
+    """The signed Euclidean distance of the level set whose inside is A >= 0 (pdeip_signed_distance_dev): positive inside, negative
+    outside, the interface half-way between an inside pixel and its outside neighbour (|out| >= 0.5).  max_dist = R > 0: values beyond
+    the band saturate at +-(R + 0.5); otherwise a plane without an interface is +-Inf.  out may be A.  Returns out."""
+    _chk(A)
+    nrows, ncols, F = _dims(A)
+    out = _typed_plane(A, out, True, torch.float32, "signed_distance: out")
+    capi.call("pdeip_signed_distance_dev", _stream(), A.data_ptr(), nrows, ncols, F, int(max_dist), out.data_ptr())
+    return out
+
+
+def nearest_fill(D, max_dist=0, out=None, filled_out=None, dist_out=None):
+    """The holes (NaN) of the resident sparse map D [(F,) ncols, nrows] take the bits of the nearest known pixel of their frame
+    (pdeip_nearest_fill_dev; ties: the lowest index); known pixels keep their bits; a hole without a source (an empty frame, or none
+    within max_dist > 0) stays NaN.  filled_out (optional) = 1 on the holes that were filled, dist_out (optional) = the distance to the
+    source.  out may be D.  Returns out.  Not a substitute for tv_inpaint4 on occlusion bands: their nearest neighbour is the foreground."""
+    _chk(D)
+    nrows, ncols, F = _dims(D)
+    out = _typed_plane(D, out, True, torch.float32, "nearest_fill: out")
+    for t, what in ((filled_out, "filled_out"), (dist_out, "dist_out")):
+        if t is not None:
+            _chk_typed(t, torch.float32, D.numel(), "nearest_fill: " + what)
+    capi.call("pdeip_nearest_fill_dev", _stream(), D.data_ptr(), nrows, ncols, F, int(max_dist), out.data_ptr(), _ptr(filled_out),
+              _ptr(dist_out))
+    return out

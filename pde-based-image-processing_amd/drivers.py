@@ -20,6 +20,7 @@ capi.MODE_RED_BLACK the parallel one).
     disp_crosscheck / flow_crosscheck / stereo_maps   this library's own: left-right and forward-backward checks (pdeip_disp_crosscheck)
     TVinpaint4                  this library's own: the holes of a sparse map filled by TV inpainting (pdeip_tv_inpaint4)
     gaussian / Diffusion8       this library's own: smoothing at a chosen scale; structure-tensor diffusion, EED and CED (pdeip_diffusion8)
+    bwdist / signed_distance / nearest_fill   this library's own: exact Euclidean distance transform (pdeip_bwdist, pdeip_signed_distance, pdeip_nearest_fill)
 
 `Us=`, `Vs=` (param.Us / param.Vs: spatial a-priori fields, double, NaN = no constraint) and `scales=` (param.scales) are taken
 by the late-linearisation flow drivers and the disparity driver as the reference's drivers take them.
@@ -990,18 +991,27 @@ def capi_TVinpaint4(D, guide=None, mode=capi.MODE_EXACT_ORDER, return_filled=Fal
 
 # ---- frame interpolation: the picture between two frames, from a computed flow (include/pdeip.h; this library's own driver) ----
 def _interp_param(who, param):
-    """(mode, InterpParams) of a driver's keyword parameters: mode, a, b, use_costs and TVinpaint4's for the hole filling."""
+    """(mode, InterpParams) of a driver's keyword parameters: mode, a, b, use_costs and TVinpaint4's for the hole filling; with
+    fill_with="nearest" (and its max_dist) the nearest-source fill, which takes none of TVinpaint4's."""
     param = dict(param)
     mode = param.pop("mode", capi.MODE_EXACT_ORDER)
+    fill_with = param.pop("fill_with", "tv")
+    if fill_with not in ("tv", "nearest"):
+        raise ValueError("%s: fill_with must be 'tv' or 'nearest' (got %r)" % (who, fill_with))
+    nearest = {}
+    if fill_with == "nearest":
+        nearest = dict(fill_with="nearest", max_dist=int(param.pop("max_dist", 0)))
     fill = {k: param.pop(k) for k in list(param) if k in INPAINT_DEFAULTS}
     unknown = set(param) - {"a", "b", "use_costs"}
     if unknown:
         raise ValueError("%s: unknown parameter %s" % (who, sorted(unknown)))
+    if nearest and fill:
+        raise ValueError("%s: fill_with='nearest' takes no TV inpainting parameters (got %s)" % (who, sorted(fill)))
     _inpaint_param(who, fill)
     for k in ("a", "b"):
         if k in param:
             param[k] = _threshold(who, k, param[k])
-    return mode, dict(param, **fill)
+    return mode, dict(param, **fill, **nearest)
 
 
 def _time(who, t):
@@ -1016,8 +1026,10 @@ def flow_interpolate(I0, I1, U, V, Ub=None, Vb=None, t=0.5, return_flow=False, r
     pdeip_flow_interpolate call (include/pdeip.h): the flow is carried forward to t (the most photo-consistent source wins a
     pixel), its holes are filled by TV inpainting, and both frames are sampled along it and blended.  With the backward flow
     (Ub, Vb) of frame 1 -> 0 the two forward-backward checks decide at an occlusion which frame alone is shown.  param: mode, a 0.01,
-    b 0.5, use_costs 1 and TVinpaint4's.  Returns It, with return_flow also the filled flow at t as [rows, cols, 2], with
-    return_source also the plane 0 neither / 1 frame 0 / 2 frame 1 / 3 both."""
+    b 0.5, use_costs 1 and TVinpaint4's; fill_with="nearest" (default "tv") fills the holes with the nearest source's flow instead
+    (pdeip_flow_interpolate_nearest; max_dist > 0: only that far, the rest becomes 0) and then refuses TVinpaint4's parameters.
+    Returns It, with return_flow also the filled flow at t as [rows, cols, 2], with return_source also the plane 0 neither / 1 frame 0
+    / 2 frame 1 / 3 both."""
     who = "flow_interpolate"
     mode, prm_kw = _interp_param(who, param)
     t = _time(who, t)
@@ -1035,11 +1047,17 @@ def flow_interpolate(I0, I1, U, V, Ub=None, Vb=None, t=0.5, return_flow=False, r
     It = np.zeros((rows, cols, C), np.float32, order="F")
     Ut, Vt = ((np.zeros((rows, cols), np.float32, order="F") for _ in range(2)) if return_flow else (None, None))
     src = np.zeros((rows, cols), np.float32, order="F") if return_source else None
+    nearest = prm_kw.pop("fill_with", "tv") == "nearest"
+    max_dist = prm_kw.pop("max_dist", 0)
     prm = dev.InterpParams.make(**prm_kw)
-    with _ordering(mode):
-        capi.call("pdeip_flow_interpolate", f0.ctypes.data, f1.ctypes.data, C, planes[0].ctypes.data, planes[1].ctypes.data,
-                  _ptr(planes[2]) if Ub is not None else None, _ptr(planes[3]) if Ub is not None else None, rows, cols, t,
-                  ctypes.addressof(prm), It.ctypes.data, _ptr(Ut), _ptr(Vt), _ptr(src))
+    head = (f0.ctypes.data, f1.ctypes.data, C, planes[0].ctypes.data, planes[1].ctypes.data, _ptr(planes[2]) if Ub is not None else None,
+            _ptr(planes[3]) if Ub is not None else None, rows, cols, t, ctypes.addressof(prm))
+    tail = (It.ctypes.data, _ptr(Ut), _ptr(Vt), _ptr(src))
+    if nearest:
+        capi.call("pdeip_flow_interpolate_nearest", *head, max_dist, *tail)
+    else:
+        with _ordering(mode):
+            capi.call("pdeip_flow_interpolate", *head, *tail)
     out = (It if i0.ndim == 3 else It[:, :, 0],)
     if return_flow:
         out += (np.stack([Ut, Vt], axis=2),)
@@ -1051,7 +1069,7 @@ def flow_interpolate(I0, I1, U, V, Ub=None, Vb=None, t=0.5, return_flow=False, r
 def interpolate_frames(Iin, channels, t=(0.5,), mode=capi.MODE_EXACT_ORDER, fstTerm="rgb", sndTerm="none", return_flows=False, **param):
     """In-between frames of Iin = cat(3, frame0, frame1): FlowEminND_llin_2D_v10's level loop forward and with the frames swapped,
     then the chain of flow_interpolate for every t, all on the device with one download at the end.  param: the flow driver's
-    parameters; the chain's go in interp=dict(...).  Returns the list of frames [rows, cols(, channels)], one per t (values on Iin's
+    parameters; the chain's go in interp=dict(...), fill_with="nearest" and its max_dist among them.  Returns the list of frames [rows, cols(, channels)], one per t (values on Iin's
     scale); with return_flows also the forward and the backward flow as [rows, cols, 2] arrays."""
     who = "interpolate_frames"
     param = dict(param)
@@ -1076,3 +1094,51 @@ def interpolate_frames(Iin, channels, t=(0.5,), mode=capi.MODE_EXACT_ORDER, fstT
         both = lambda a, b: np.stack([dev.to_matlab(a), dev.to_matlab(b)], axis=2)
         return out, both(Uf, Vf), both(Ub, Vb)
     return out
+
+
+# ---- exact Euclidean distance transform: bwdist, signed distance, nearest fill (include/pdeip.h; this library's own calls) ----
+def _edt_planes(who, A):
+    a = np.asfortranarray(np.asarray(A, dtype=np.float32))
+    if a.ndim not in (2, 3):
+        raise ValueError("%s: the input must be [rows, cols] or [rows, cols, frames] (got %s)" % (who, a.shape))
+    return a, a.shape[0], a.shape[1], (a.shape[2] if a.ndim == 3 else 1)
+
+
+def bwdist(BW):
+    """[D, IDX] = bwdist(BW) with the Euclidean metric, one pdeip_bwdist call.  BW [rows, cols(, frames)]: a logical array, or numbers
+    of which the positive ones are the features (as bwlabel takes them).  Returns (D single: the distance to the nearest feature, IDX
+    int32: its 0-based column-major linear index within the frame; MATLAB's is 1-based).  Among equidistant features the lowest index
+    wins.  A frame without a feature is +Inf and -1."""
+    B = np.asarray(BW)
+    a, rows, cols, F = _edt_planes("bwdist", (B > 0).astype(np.float32))
+    D = np.empty(a.shape, np.float32, order="F")
+    IDX = np.empty(a.shape, np.int32, order="F")
+    capi.call("pdeip_bwdist", a.ctypes.data, rows, cols, F, D.ctypes.data, IDX.ctypes.data)
+    return D, IDX
+
+
+def signed_distance(A, max_dist=0):
+    """The signed Euclidean distance of the level set whose inside is A >= 0, one pdeip_signed_distance call: positive inside, negative
+    outside, the interface half-way between an inside pixel and its outside neighbour (so |out| >= 0.5).  The usual start of a level
+    set: GAC_v10a(I, signed_distance(PHI)) where runme.m hands over PHI = +-1 and lets Reinit straighten a band of ten pixels.
+    max_dist = R > 0 looks R pixels far and saturates at +-(R + 0.5) beyond; otherwise a plane without an interface is +-Inf.
+    A [rows, cols(, frames)]; returns single."""
+    a, rows, cols, F = _edt_planes("signed_distance", A)
+    out = np.empty(a.shape, np.float32, order="F")
+    capi.call("pdeip_signed_distance", a.ctypes.data, rows, cols, F, int(max_dist), out.ctypes.data)
+    return out
+
+
+def nearest_fill(D, max_dist=0, return_filled=False, return_dist=False):
+    """Fill the holes (NaN) of the sparse map D [rows, cols(, frames)] with the nearest known pixel of the same frame, one
+    pdeip_nearest_fill call: known pixels keep their bits, ties go to the lowest column-major index, a hole without a source (an empty
+    frame, or none within max_dist > 0 pixels) stays NaN.  The cheapest well-defined fill -- thin cracks, the holes of a splat -- and
+    NOT a substitute for TVinpaint4 on occlusion bands, whose nearest neighbour is the foreground.  Returns the filled map, with
+    return_filled also the plane that is 1 on the filled holes, with return_dist also the distance to the source."""
+    d, rows, cols, F = _edt_planes("nearest_fill", D)
+    out = np.empty(d.shape, np.float32, order="F")
+    filled = np.empty(d.shape, np.float32, order="F") if return_filled else None
+    dist = np.empty(d.shape, np.float32, order="F") if return_dist else None
+    capi.call("pdeip_nearest_fill", d.ctypes.data, rows, cols, F, int(max_dist), out.ctypes.data, _ptr(filled), _ptr(dist))
+    res = (out,) + ((filled,) if return_filled else ()) + ((dist,) if return_dist else ())
+    return res[0] if len(res) == 1 else res
