@@ -1329,6 +1329,55 @@ int pdeip_flow_interpolate_nearest(const float *I0, const float *I1, int channel
                                    const float *Vb, int nrows, int ncols, double t, const pdeip_interp_params *prm, int max_dist,
                                    float *It_out, float *Ut_out, float *Vt_out, float *source_out);
 
+/* ---- primal-dual total variation: TV-L1, ROF, Huber-TV (csrc/pdeip_tvpd.hip) ---------------------------------------------------------
+ *
+ * This library's own call (the reference's TVdenoise4 / TVdenoise8 are lagged-diffusivity TV with a quadratic data term): the
+ * first-order primal-dual iteration of Chambolle and Pock for  min_u  TV(u) + lambda |u - f|  (PDEIP_TVPD_L1, which rejects outliers)
+ * or  TV(u) + lambda/2 (u - f)^2  (PDEIP_TVPD_L2, ROF), with the Huber norm in place of TV when huber > 0.  No linear solver, no
+ * pyramid, no eps.  Planes are column-major float32 [nrows x ncols x frames], i the contiguous row index; each frame on its own.
+ * The contract, in float32 without contraction, / and sqrt correctly rounded, in exactly this order; tl = tau lambda, 1 + tl and
+ * 1 + sigma huber are each formed once on the host in float32 (tests/tvpd_ref.py restates it, and the device equals it bit for bit).
+ * Start: u = u_prev = the start, px = py = 0.  Each of the `iter` iterations:
+ *   ub       = (u + u) - u_prev
+ *   gx[i,j]  = ub[i+1,j] - ub[i,j]   (0 on the last row);   gy[i,j] = ub[i,j+1] - ub[i,j]   (0 on the last column)
+ *   qx       = px + sigma gx;  qy = py + sigma gy;   huber > 0:  qx = qx / (1 + sigma huber), qy likewise
+ *   n        = s > 1 ? s : 1  with  s = sqrt(qx qx + qy qy)      (max(1, s); a NaN norm divides by 1)
+ *   px'      = qx / n;  py' = qy / n
+ *   d        = (px'[i,j] - px'[i-1,j]) + (py'[i,j] - py'[i,j-1])   (a missing neighbour: the term is px'[i,j] / py'[i,j] alone)
+ *   v        = u + tau d
+ *   L2:  u' = (v + tl f) / (1 + tl)
+ *   L1:  u' = v - tl  if v - f > tl;   v + tl  if v - f < -tl;   f  otherwise
+ *   f is NaN (no data here):  u' = v
+ *   u_prev'  = u
+ * px stays exactly 0 on the last row and py on the last column, so 1 x N, N x 1 and 1 x 1 planes need no special case.  +-Inf in f is
+ * data; what comes of it is whatever the recurrence gives.
+ * The start is u0 if given; with u0 == NULL it is f with its NaNs replaced by pdeip_nearest_fill's result (a frame without a known
+ * pixel stays NaN).  iter = 0 returns the start.  tau, sigma: NaN = the defaults 0.25 and 0.5 (tau sigma 8 = 1, both exact in binary).
+ * _dev: device pointers, launches on `stream`, nothing read back, graph-capturable once an eager call has created the workspaces
+ * (nine planes of its own, and pdeip_nearest_fill's for the start).  f and u0 are never written; planes may start at any 4-byte offset.
+ * Kernels: k_tvpd_step does one iteration per launch, k_tvpd_block<T> does T per launch on LDS tiles with a halo of T; both give the
+ * same bits.  Environment PDEIP_TVPD_STEPS: unset or 0 the library's choice, 1 single steps, 2 / 4 / 8 blocks of that many.
+ * Launches (pdeip_last_launch_count()), a function of iter, T and u0 == NULL alone, with T = 1 for single steps:
+ *   [3 with u0 == NULL]  +  (T > 1 ? iter / T + iter % T : iter);   iter = 0:  3 with u0 == NULL, 1 (a copy) otherwise.
+ * pdeip_set_mode does not apply.
+ * Refused with PDEIP_ERR_ARG before any HIP call: a NULL f, u_out or prm; u_out equal to f or u0; a side or frames < 1; more than
+ * 2^31-1 elements; an unknown model; lambda or huber negative or not finite; iter < 0; tau or sigma not positive and finite;
+ * tau sigma 8 > 1 (evaluated in double); an unsupported PDEIP_TVPD_STEPS.  PDEIP_ERR_UNSUPPORTED: more than 65535 columns or frames. */
+#define PDEIP_TVPD_L1 0
+#define PDEIP_TVPD_L2 1
+typedef struct {
+    int model;     /* PDEIP_TVPD_L1, PDEIP_TVPD_L2 */
+    double lambda; /* data weight */
+    double huber;  /* 0 = TV, > 0 = Huber-TV */
+    int iter;
+    double tau;   /* NaN = default */
+    double sigma; /* NaN = default */
+} pdeip_tvpd_params;
+int pdeip_tv_pd_dev(void *stream, const float *f, const float *u0 /* or NULL */, int nrows, int ncols, int frames,
+                    const pdeip_tvpd_params *prm, float *u_out);
+/* the same without `stream`, on host pointers */
+int pdeip_tv_pd(const float *f, const float *u0, int nrows, int ncols, int frames, const pdeip_tvpd_params *prm, float *u_out);
+
 /* ---- structure-tensor anisotropic diffusion (csrc/pdeip_stensor.hip) --------------------------------------------------------
  * Weickert's edge-enhancing (EED) and coherence-enhancing (CED) diffusion, each semi-implicit step (I - tau A(u^k)) u^{k+1} = u^k
  * one PDEsolver8 solve by pdeip_pde_sor8_dev / pdeip_pde_alr8_dev.  Not in the reference toolbox; tests/stensor_ref.py restates

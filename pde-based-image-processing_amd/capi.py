@@ -21,6 +21,7 @@ SEG_SURFACE, SEG_GREEDY, SEG_INVERSE = 0, 1, 2  # PDEIP_SEG_*: the competition s
 MODE_LINE_SCAN = 2  # line relaxation in the reference's line order, a line's recurrences as parallel scans
 # PDEIP_EDT_*: which pixels are the features of the distance transform; + 4: the complement
 EDT_POSITIVE, EDT_NONNEG, EDT_NOT_NAN, EDT_POSITIVE_NOT, EDT_NONNEG_NOT, EDT_NOT_NAN_NOT = 0, 1, 2, 4, 5, 6
+TVPD_L1, TVPD_L2 = 0, 1  # PDEIP_TVPD_*: the data term of primal-dual TV
 
 _P = ctypes.c_void_p  # float* (host or device), passed as an address
 _I = ctypes.c_int
@@ -206,6 +207,9 @@ SIGNATURES = {
     "pdeip_nearest_fill": [_P, _I, _I, _I, _I, _P, _P, _P],
     "pdeip_flow_interpolate_nearest_dev": [_P, _P, _P, _I, _P, _P, _P, _P, _I, _I, ctypes.c_double, _P, _I, _P, _P, _P, _P],
     "pdeip_flow_interpolate_nearest": [_P, _P, _I, _P, _P, _P, _P, _I, _I, ctypes.c_double, _P, _I, _P, _P, _P, _P],
+    # primal-dual total variation (csrc/pdeip_tvpd.hip)
+    "pdeip_tv_pd_dev": [_P, _P, _P, _I, _I, _I, _P, _P],
+    "pdeip_tv_pd": [_P, _P, _I, _I, _I, _P, _P],
     # structure-tensor anisotropic diffusion (csrc/pdeip_stensor.hip)
     "pdeip_gauss_taps": [ctypes.c_double, _P, _I, ctypes.POINTER(ctypes.c_int)],
     "pdeip_gauss": [_P, _I, _I, _I, ctypes.c_double, _P],

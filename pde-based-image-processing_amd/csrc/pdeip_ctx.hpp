@@ -21,7 +21,7 @@
 
 namespace pdeip {
 
-enum { WS_AUX0 = 0, WS_AUX1, WS_PING, WS_ARENA, WS_CTL, WS_ORDER, WS_ALR, WS_ALR_T, WS_TV, WS_SMALL, WS_MAIL, WS_PACK, WS_DRIVER, WS_LEX, WS_LS, WS_RANSAC, WS_SEG_STAGE, WS_SEG, WS_SEG_RC, WS_CCL, WS_SEEDS, WS_SELECT, WS_GAC, WS_RANSAC_BATCH, WS_FLOWVIZ, WS_CROSSCHECK, WS_INTERP, WS_GAUSS, WS_STENSOR, WS_EDT, WS_NSLOT };
+enum { WS_AUX0 = 0, WS_AUX1, WS_PING, WS_ARENA, WS_CTL, WS_ORDER, WS_ALR, WS_ALR_T, WS_TV, WS_SMALL, WS_MAIL, WS_PACK, WS_DRIVER, WS_LEX, WS_LS, WS_RANSAC, WS_SEG_STAGE, WS_SEG, WS_SEG_RC, WS_CCL, WS_SEEDS, WS_SELECT, WS_GAC, WS_RANSAC_BATCH, WS_FLOWVIZ, WS_CROSSCHECK, WS_INTERP, WS_GAUSS, WS_STENSOR, WS_EDT, WS_TVPD, WS_NSLOT };
 
 constexpr int MAX_DEVICES = 16;
 

@@ -1257,3 +1257,38 @@ def nearest_fill(D, max_dist=0, out=None, filled_out=None, dist_out=None):
     capi.call("pdeip_nearest_fill_dev", _stream(), D.data_ptr(), nrows, ncols, F, int(max_dist), out.data_ptr(), _ptr(filled_out),
               _ptr(dist_out))
     return out
+
+
+# ---- primal-dual total variation: TV-L1, ROF, Huber-TV (csrc/pdeip_tvpd.hip) ----
+TVPD_MODELS = {"l1": capi.TVPD_L1, "l2": capi.TVPD_L2}
+
+
+class TvpdParams(ctypes.Structure):
+    """pdeip_tvpd_params: model PDEIP_TVPD_L1 / _L2, the data weight lambda, huber (0 = TV), iter, tau and sigma (NaN = 0.25 and 0.5)."""
+    _fields_ = [("model", ctypes.c_int), ("lambda_", ctypes.c_double), ("huber", ctypes.c_double), ("iter", ctypes.c_int), ("tau", ctypes.c_double),
+                ("sigma", ctypes.c_double)]
+
+    @classmethod
+    def make(cls, model, lam, iter, huber=0.0, tau=None, sigma=None, who="tv_pd"):
+        if isinstance(model, str) and model.lower() not in TVPD_MODELS:
+            raise ValueError("%s: model must be 'l1' or 'l2' (got %r)" % (who, model))
+        nan = float("nan")
+        return cls(int(TVPD_MODELS[model.lower()] if isinstance(model, str) else model), float(lam), float(huber), int(iter),
+                   nan if tau is None else float(tau), nan if sigma is None else float(sigma))
+
+
+def tv_pd(f, model, lam, iter, huber=0, u0=None, tau=None, sigma=None, out=None):
+    """Primal-dual total variation of the resident plane f [(F,) ncols, nrows] (pdeip_tv_pd_dev), every frame on its own: `iter`
+    iterations of Chambolle and Pock's method for TV + lam |u - f| (model 'l1', which rejects outliers) or TV + lam/2 (u - f)^2 ('l2',
+    ROF), Huber-TV with huber > 0.  NaN in f means no data there.  The start is u0, or f with its holes filled from the nearest known
+    pixel.  tau, sigma: None = 0.25 and 0.5.  f and u0 are not modified; out must be neither.  Returns out.  Nothing is read back."""
+    _chk(f)
+    prm = TvpdParams.make(model, lam, iter, huber, tau, sigma)
+    nrows, ncols, F = _dims(f)
+    if u0 is not None:
+        _chk(u0)
+        if u0.shape != f.shape:
+            raise capi.PdeipError(capi.PDEIP_ERR_ARG, "tv_pd: u0 is %s but f is %s" % (tuple(u0.shape), tuple(f.shape)))
+    out = _out_plane(f, out, True, "tv_pd: out")
+    capi.call("pdeip_tv_pd_dev", _stream(), f.data_ptr(), _ptr(u0), nrows, ncols, F, ctypes.addressof(prm), out.data_ptr())
+    return out

@@ -21,6 +21,7 @@ capi.MODE_RED_BLACK the parallel one).
     TVinpaint4                  this library's own: the holes of a sparse map filled by TV inpainting (pdeip_tv_inpaint4)
     gaussian / Diffusion8       this library's own: smoothing at a chosen scale; structure-tensor diffusion, EED and CED (pdeip_diffusion8)
     bwdist / signed_distance / nearest_fill   this library's own: exact Euclidean distance transform (pdeip_bwdist, pdeip_signed_distance, pdeip_nearest_fill)
+    TVdenoisePD                 this library's own: primal-dual total variation, TV-L1 / ROF / Huber-TV (pdeip_tv_pd)
 
 `Us=`, `Vs=` (param.Us / param.Vs: spatial a-priori fields, double, NaN = no constraint) and `scales=` (param.scales) are taken
 by the late-linearisation flow drivers and the disparity driver as the reference's drivers take them.
@@ -1142,3 +1143,38 @@ def nearest_fill(D, max_dist=0, return_filled=False, return_dist=False):
     capi.call("pdeip_nearest_fill", d.ctypes.data, rows, cols, F, int(max_dist), out.ctypes.data, _ptr(filled), _ptr(dist))
     res = (out,) + ((filled,) if return_filled else ()) + ((dist,) if return_dist else ())
     return res[0] if len(res) == 1 else res
+
+
+# ---- primal-dual total variation: TV-L1, ROF, Huber-TV (include/pdeip.h; this library's own call) ----
+def _tvpd_inputs(who, I, u0):
+    f, rows, cols, F = _edt_planes(who, I)
+    s = None
+    if u0 is not None:
+        s = np.asfortranarray(np.asarray(u0, dtype=np.float32))
+        if s.shape != f.shape:
+            raise ValueError("%s: u0 is %s but the input is %s" % (who, s.shape, f.shape))
+    return f, s, rows, cols, F
+
+
+def TVdenoisePD(I, model="l1", lam=0.8, iter=300, huber=0.0, u0=None, tau=None, sigma=None):
+    """Total-variation denoising by the first-order primal-dual iteration of Chambolle and Pock, resident on the device
+    (device.tv_pd).  I [rows, cols(, frames)] of any numeric type, taken as single; NaN means no data.  model 'l1': TV + lam |u - I|,
+    which rejects gross outliers where a quadratic data term averages them in; 'l2': TV + lam/2 (u - I)^2 (ROF); huber > 0: the Huber
+    norm in place of TV, which takes the staircase out of slopes.  The start is u0, or I with its holes filled from the nearest known
+    pixel.  tau, sigma: None = 0.25 and 0.5 (tau sigma 8 <= 1).  No pyramid, no linear solver, no eps.  Returns single."""
+    who = "TVdenoisePD"
+    prm = dev.TvpdParams.make(model, lam, iter, huber, tau, sigma, who=who)
+    f, s, _, _, _ = _tvpd_inputs(who, I, u0)
+    out = dev.tv_pd(dev.to_device(f), prm.model, lam, iter, huber, None if s is None else dev.to_device(s), tau, sigma)
+    dev.sync_check()
+    return dev.to_matlab(out)
+
+
+def capi_TVdenoisePD(I, model="l1", lam=0.8, iter=300, huber=0.0, u0=None, tau=None, sigma=None):
+    """pdeip_tv_pd on MATLAB-shaped numpy arrays: TVdenoisePD through the host entry point, same bits."""
+    who = "capi_TVdenoisePD"
+    prm = dev.TvpdParams.make(model, lam, iter, huber, tau, sigma, who=who)
+    f, s, rows, cols, F = _tvpd_inputs(who, I, u0)
+    out = np.empty(f.shape, np.float32, order="F")
+    capi.call("pdeip_tv_pd", f.ctypes.data, _ptr(s), rows, cols, F, ctypes.addressof(prm), out.ctypes.data)
+    return out
