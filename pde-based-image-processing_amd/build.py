@@ -30,7 +30,7 @@ UNITS = {
     "pdeip_multi.hip": [],
     "pdeip_levelset.hip": ["pdeip_levelset.hpp", "pdeip_cv.hpp", "pdeip_thomas.hpp"],
     "pdeip_diffusion.hip": ["pdeip_models.hpp", "pdeip_pointwise.hpp", "pdeip_diffusion.hpp", "pdeip_thomas.hpp"],
-    "pdeip_ransac.hip": ["pdeip_ransac.hpp", "pdeip_ransac_batch.hpp", "pdeip_reduce.hpp"],
+    "pdeip_ransac.hip": ["pdeip_ransac.hpp", "pdeip_reduce.hpp"],
     "pdeip_segmentation.hip": ["pdeip_segmentation.hpp", "pdeip_reduce.hpp", "pdeip_seeds_plan.hpp", "pdeip_sparse_plan.hpp"],
     "pdeip_sparse.hip": ["pdeip_sparse.hpp", "pdeip_cswap.hpp", "pdeip_models.hpp", "pdeip_pointwise.hpp", "pdeip_sparse_plan.hpp", "pdeip_seeds_plan.hpp"],
     "pdeip_ccl.hip": ["pdeip_ccl.hpp", "pdeip_ccl_plan.hpp"],

@@ -1,12 +1,22 @@
 // pdeip_ransac.hpp -- kernels of SurfaceEquation: the RANSAC fit of z = f(x, y), f a first- or second-order polynomial
-// (mex/source/SurfaceEquation.c + mex/source/library/ransac.c).  The contract is in include/pdeip.h; tests/ransac_ref.py restates it.
+// (mex/source/SurfaceEquation.c + mex/source/library/ransac.c).  The contract is in include/pdeip.h; tests/ransac_ref.py and
+// tests/ransac_batch_ref.py restate it.
 //
-// One call is a chain on one stream: k_ransac_fit (one thread per hypothesis: gather, float64 Householder QR, model slot) ->
-// k_ransac_score (data tiles x hypothesis groups: inlier count and float64 error sum per (tile, hypothesis), stored, no atomics) ->
-// k_ransac_select (one workgroup: sums the partials in tile order, one thread applies RANSAC()'s rules in hypothesis order) ->
-// k_ransac_errors (the winner's error vector).  The masked form puts k_mask_count / k_mask_scan / k_mask_scatter in front
-// (PHI >= 0 ranked in column-major order, rows [X Y 1] or [X^2 Y^2 XY X Y 1]) and k_ransac_dist behind (the error of every pixel).
-// The number of data rows may live on the device (the masked form): every kernel takes it as a value and as a pointer.
+// One call is a chain on one stream, the segment on a grid axis of every stage (S = 1 for the single calls):
+//   k_mask_count    grid (256-pixel blocks, S)         block counts of PHI_s >= 0                       } the masked forms:
+//   k_mask_scan     grid (S)                           exclusive scan of a segment's block counts,      } pixels ranked in
+//                                                      ndata[s] stays on the device                     } column-major order
+//   k_mask_scatter  grid (256-pixel blocks, S)         idx[s][rank(p)] = p                              }
+//   k_ransac_fit    grid (ceil(S*H / 64))              one thread per (segment, slot), packed: gather, float64 Householder QR, model slot
+//   k_ransac_score  grid (tiles, hypothesis groups, S) inlier count and float64 error sum per (tile, hypothesis), stored, no atomics;
+//                                                      a block whose first row lies at or past the segment's count exits at once
+//   k_ransac_select grid (S)                           sums the partials in tile order, one thread applies RANSAC()'s rules in
+//                                                      hypothesis order
+//   k_ransac_errors                                    the winner's error vector (the rows-given form)
+//   k_ransac_dist   grid (256-pixel blocks, S)         the error of every pixel (the masked forms)
+// Fit and score take their data rows from a row source: GivenRows reads the caller's matrix, PixelRows re-forms the row of a
+// ranked pixel ([X Y 1] or [X^2 Y^2 XY X Y 1]) and reads D there -- a pixel's row depends on its position only, so the compaction
+// keeps indices, not rows.  The number of data rows may live on the device (the masked forms): see rows_of.
 #pragma once
 #include "pdeip_ctx.hpp"
 #include "pdeip_reduce.hpp"
@@ -23,7 +33,8 @@ constexpr int RS_SLOT = 8;     // floats of a model slot: coefficients [0..5], [
 constexpr int RS_SEL_BLOCK = 1024;
 constexpr int RS_SEL_CHUNK = 2048; // hypotheses whose totals k_ransac_select holds in LDS at a time
 
-__device__ __forceinline__ int rows_of(int ndata_h, const int *ndata_d) { return ndata_d ? *ndata_d : ndata_h; }
+// The rows of segment s: counted on the device (the masked forms) or known on the host (the rows-given form).
+__device__ __forceinline__ int rows_of(int ndata_h, const int *ndata_d, size_t s) { return ndata_d ? ndata_d[s] : ndata_h; }
 
 // The output function of SplitMix64 on the state x (Steele, Lea, Flood 2014): next() of a generator whose state is x.
 __device__ __forceinline__ unsigned long long splitmix64(unsigned long long x)
@@ -56,6 +67,37 @@ __device__ __forceinline__ void pixel_row(int i, int j, float (&a)[NC])
         a[0] = (float)(X * X); a[1] = (float)(Y * Y); a[2] = (float)(X * Y); a[NC - 3] = (float)X; a[NC - 2] = (float)Y; a[NC - 1] = 1.0f;
     }
 }
+
+// ---- row sources: load(s, r, ok, a, b) is row r of segment s, zeros where !ok (nothing is read then) ------------------------------
+// SurfaceEquation's caller-supplied matrix (S = 1): columns lda apart.
+struct GivenRows {
+    const float *A, *B;
+    int lda;
+    template <int NC>
+    __device__ __forceinline__ void load(size_t, long long r, bool ok, float (&a)[NC], float &b) const
+    {
+#pragma unroll
+        for (int c = 0; c < NC; c++) a[c] = ok ? A[(size_t)c * lda + r] : 0.0f;
+        b = ok ? B[r] : 0.0f;
+    }
+};
+
+// The pixels with PHI_s >= 0 by rank (idx[s*lda + r], k_mask_scatter) over the one data plane D of nrows rows.
+struct PixelRows {
+    const int *idx;
+    int lda;
+    const float *D;
+    int nrows;
+    template <int NC>
+    __device__ __forceinline__ void load(size_t s, long long r, bool ok, float (&a)[NC], float &b) const
+    {
+        const unsigned p = ok ? (unsigned)idx[s * lda + r] : 0u, n = (unsigned)nrows; // unsigned: the cheaper division
+        pixel_row<NC>((int)(p % n), (int)(p / n), a);
+#pragma unroll
+        for (int c = 0; c < NC; c++) a[c] = ok ? a[c] : 0.0f;
+        b = ok ? D[p] : 0.0f;
+    }
+};
 
 // ---- fit: slot 0 is the given model (singular when there is none), slot 1 + h hypothesis h ------------------------------------
 // Householder QR in float64 without pivoting on the n = NC + 1 samples, every sum in ascending row (column) index, no contraction:
@@ -110,42 +152,49 @@ __device__ __forceinline__ void fit_solve(double (&R)[NC + 1][NC + 1], bool sing
     out[7] = 0.0f;
 }
 
-template <int NC>
-__global__ void __launch_bounds__(64) k_ransac_fit(const float *__restrict__ A, const float *__restrict__ B, int lda, int ndata_h,
-                                                   const int *__restrict__ ndata_d, const unsigned *__restrict__ sets,
-                                                   unsigned long long seed, int iter, const float *__restrict__ M_in,
-                                                   float *__restrict__ models)
+// Thread t of the grid is slot t % H of segment t / H, on the segment's rows, count, given model and seed (seed + seed_stride*s).
+// The order-2 solve holds 7 x 7 doubles and sits just below 128 VGPRs; amdgpu_waves_per_eu(4) keeps the allocator from trading its
+// four waves per SIMD for a shorter schedule (order 1 needs 59 and is not affected).
+template <int NC, class Src>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4)))
+k_ransac_fit(Src src, int ndata_h, const int *__restrict__ ndata_d, int S, const unsigned *__restrict__ sets, unsigned long long seed,
+             unsigned long long seed_stride, int H, const float *__restrict__ M_in, float *__restrict__ models)
 {
     constexpr int N = NC + 1;
-    const int slot = blockIdx.x * 64 + threadIdx.x;
-    if (slot > iter) return;
-    float *out = models + (size_t)slot * RS_SLOT;
+    const long long t = (long long)blockIdx.x * 64 + threadIdx.x;
+    if (t >= (long long)S * H) return;
+    const int seg = (int)(t / H), slot = (int)(t - (long long)seg * H);
+    float *out = models + (size_t)t * RS_SLOT;
     if (slot == 0) {
+        const float *given = M_in != nullptr ? M_in + (size_t)seg * NC : nullptr;
 #pragma unroll
-        for (int c = 0; c < 6; c++) out[c] = (M_in != nullptr && c < NC) ? M_in[c] : 0.0f;
-        out[6] = M_in != nullptr ? 0.0f : 1.0f;
+        for (int c = 0; c < 6; c++) out[c] = (given != nullptr && c < NC) ? given[c] : 0.0f;
+        out[6] = given != nullptr ? 0.0f : 1.0f;
         out[7] = 0.0f;
         return;
     }
-    const unsigned ndata = (unsigned)rows_of(ndata_h, ndata_d);
-    const unsigned long long h = (unsigned long long)(slot - 1);
+    const unsigned ndata = (unsigned)rows_of(ndata_h, ndata_d, seg);
+    const unsigned long long sd = seed + seed_stride * (unsigned long long)seg, h = (unsigned long long)(slot - 1);
     double R[N][NC + 1]; // column NC: the right-hand side
     bool singular = false;
 #pragma unroll
     for (int k = 0; k < N; k++) {
-        unsigned idx;
-        if (sets != nullptr) idx = sets[h * N + k];
-        else idx = (unsigned)(((splitmix64(seed + h * N + k) >> 32) * (unsigned long long)ndata) >> 32);
-        const bool ok = idx < ndata;
+        unsigned r;
+        if (sets != nullptr) r = sets[h * N + k];
+        else r = (unsigned)(((splitmix64(sd + h * N + k) >> 32) * (unsigned long long)ndata) >> 32);
+        const bool ok = r < ndata;
         singular = singular || !ok;
+        float a[NC], b;
+        src.template load<NC>(seg, r, ok, a, b);
 #pragma unroll
-        for (int c = 0; c < NC; c++) R[k][c] = ok ? (double)A[(size_t)c * lda + idx] : 0.0;
-        R[k][NC] = ok ? (double)B[idx] : 0.0;
+        for (int c = 0; c < NC; c++) R[k][c] = (double)a[c];
+        R[k][NC] = (double)b;
     }
     fit_solve<NC>(R, singular, out);
 }
 
-// ---- score: grid (data tiles, hypothesis groups); a tile is RS_BLOCK * R rows, thread t holds rows row0 + r*RS_BLOCK + t ----------
+// ---- score: grid (data tiles, hypothesis groups, segments); a tile is RS_BLOCK * R rows, thread t holds rows
+// row0 + r*RS_BLOCK + t.
 // Per hypothesis: the thread's float64 sum over its inlier rows in ascending r, the xor butterfly over the wave (partners 32, 16,
 // .. 1 lanes apart), the four waves in ascending order; the count by ballot + popcount.  One (count, sum) per (tile, hypothesis) is
 // stored.  The butterfly runs on eight hypotheses at a time: in its first three steps a lane passes on the partial of the
@@ -217,14 +266,16 @@ __device__ __forceinline__ void score_rows(const float (&a)[R][NC], const float 
     }
 }
 
-template <int NC, int R>
-__global__ void __launch_bounds__(RS_BLOCK) k_ransac_score(const float *__restrict__ A, const float *__restrict__ B, int lda, int ndata_h,
-                                                           const int *__restrict__ ndata_d, const float *__restrict__ models, int H,
-                                                           int G, float thr2, double *__restrict__ psum, int *__restrict__ pcnt)
+// The rows are formed once per block, before the hypotheses.
+template <int NC, int R, class Src>
+__global__ void __launch_bounds__(RS_BLOCK) k_ransac_score(Src src, int ndata_h, const int *__restrict__ ndata_d,
+                                                           const float *__restrict__ models, int H, int G, float thr2,
+                                                           double *__restrict__ psum, int *__restrict__ pcnt)
 {
-    const int ndata = rows_of(ndata_h, ndata_d);
+    const size_t seg = blockIdx.z;
+    const int ndata = rows_of(ndata_h, ndata_d, seg);
     const long long row0 = (long long)blockIdx.x * (RS_BLOCK * R);
-    if (row0 >= ndata) return; // the masked form sizes the grid for every pixel
+    if (row0 >= ndata) return; // the masked forms size the grid for every pixel: most blocks of a small segment
     const int tid = threadIdx.x;
     const int h0 = blockIdx.y * G;
     const int ng = min(G, H - h0);
@@ -234,14 +285,13 @@ __global__ void __launch_bounds__(RS_BLOCK) k_ransac_score(const float *__restri
     for (int r = 0; r < R; r++) {
         const long long row = row0 + (long long)r * RS_BLOCK + tid;
         ok[r] = row < ndata;
-#pragma unroll
-        for (int c = 0; c < NC; c++) a[r][c] = ok[r] ? A[(size_t)c * lda + row] : 0.0f;
-        b[r] = ok[r] ? B[row] : 0.0f;
+        src.template load<NC>(seg, row, ok[r], a[r], b[r]);
     }
-    score_rows<NC, R>(a, b, ok, models + (size_t)h0 * RS_SLOT, ng, thr2, psum + ((size_t)blockIdx.x * H + h0), pcnt + ((size_t)blockIdx.x * H + h0));
+    const size_t at = (seg * gridDim.x + blockIdx.x) * H + h0;
+    score_rows<NC, R>(a, b, ok, models + (seg * H + h0) * RS_SLOT, ng, thr2, psum + at, pcnt + at);
 }
 
-// ---- select: one workgroup ------------------------------------------------------------------------------------------------------
+// ---- select: one workgroup per segment ------------------------------------------------------------------------------------------
 // Totals: per hypothesis the tile partials in ascending tile order.  Then thread 0 walks the slots in order with RANSAC()'s rules
 // (ransac.c:112-211) and writes the winner's slot to `win` and its coefficients to M_out.
 __device__ __forceinline__ void select_winner(const double *__restrict__ psum, const int *__restrict__ pcnt, int H, int ndata, int tile_rows,
@@ -310,35 +360,35 @@ __device__ __forceinline__ void select_winner(const double *__restrict__ psum, c
     }
 }
 
-__global__ void __launch_bounds__(RS_SEL_BLOCK) k_ransac_select(const double *__restrict__ psum, const int *__restrict__ pcnt, int H,
+// `tiles`: the tiles the score grid had, the partials of a segment that far apart.
+__global__ void __launch_bounds__(RS_SEL_BLOCK) k_ransac_select(const double *__restrict__ psum, const int *__restrict__ pcnt, int H, int tiles,
                                                                 int ndata_h, const int *__restrict__ ndata_d, int tile_rows,
                                                                 const float *__restrict__ models, int has_given, float min_set_size,
                                                                 int ncoef, float *__restrict__ M_out, float *__restrict__ win,
                                                                 int *__restrict__ inliers_out, double *__restrict__ errsum_out)
 {
-    select_winner(psum, pcnt, H, rows_of(ndata_h, ndata_d), tile_rows, models, has_given, min_set_size, ncoef, M_out, win, inliers_out, errsum_out);
+    const size_t seg = blockIdx.x;
+    select_winner(psum + seg * tiles * H, pcnt + seg * tiles * H, H, rows_of(ndata_h, ndata_d, seg), tile_rows, models + seg * H * RS_SLOT,
+                  has_given, min_set_size, ncoef, M_out + seg * ncoef, win + seg * RS_SLOT, inliers_out ? inliers_out + seg * H : nullptr,
+                  errsum_out ? errsum_out + seg * H : nullptr);
 }
 
-// ---- the winner's errors --------------------------------------------------------------------------------------------------------
+// ---- the winner's errors on the given rows --------------------------------------------------------------------------------------
 template <int NC>
-__global__ void __launch_bounds__(RS_BLOCK) k_ransac_errors(const float *__restrict__ A, const float *__restrict__ B, int lda, int ndata_h,
-                                                            const int *__restrict__ ndata_d, const float *__restrict__ win,
-                                                            float *__restrict__ err_out)
+__global__ void __launch_bounds__(RS_BLOCK) k_ransac_errors(GivenRows src, int ndata, const float *__restrict__ win, float *__restrict__ err_out)
 {
-    const int ndata = rows_of(ndata_h, ndata_d);
     const long long row = (long long)blockIdx.x * RS_BLOCK + threadIdx.x;
     if (row >= ndata) return;
-    float a[NC], m[NC];
+    float a[NC], b, m[NC];
+    src.load<NC>(0, row, true, a, b);
 #pragma unroll
-    for (int c = 0; c < NC; c++) {
-        a[c] = A[(size_t)c * lda + row];
-        m[c] = win[c];
-    }
-    err_out[row] = win[6] != 0.0f ? FLT_MAX : row_error<NC>(a, B[row], m);
+    for (int c = 0; c < NC; c++) m[c] = win[c];
+    err_out[row] = win[6] != 0.0f ? FLT_MAX : row_error<NC>(a, b, m);
 }
 
-// ---- the masked form ------------------------------------------------------------------------------------------------------------
-// Pixels in memory (column-major) order; PHI >= 0 is false for a NaN.  One block ranks RS_BLOCK pixels.
+// ---- the masked forms: S level-set planes (npix apart) over one data plane --------------------------------------------------------
+// Pixels in memory (column-major) order; PHI >= 0 is false for a NaN.  One block ranks RS_BLOCK pixels.  Segment s has its block
+// counts at blk + s*ldb and its ranked pixels at idx + s*lda.
 __device__ __forceinline__ void mask_count(const float *__restrict__ PHI, int npix, int *__restrict__ blk_cnt)
 {
     __shared__ int s_w[RS_WAVES];
@@ -350,9 +400,10 @@ __device__ __forceinline__ void mask_count(const float *__restrict__ PHI, int np
     if (threadIdx.x == 0) blk_cnt[blockIdx.x] = (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
 }
 
-__global__ void __launch_bounds__(RS_BLOCK) k_mask_count(const float *__restrict__ PHI, int npix, int *__restrict__ blk_cnt)
+__global__ void __launch_bounds__(RS_BLOCK) k_mask_count(const float *__restrict__ PHI, int npix, int *__restrict__ blk, int ldb)
 {
-    mask_count(PHI, npix, blk_cnt);
+    const size_t s = blockIdx.y;
+    mask_count(PHI + s * npix, npix, blk + s * ldb);
 }
 
 // Exclusive prefix sum of the block counts, in place, by one workgroup; the total goes to ndata[0] and ndata_out[0].
@@ -386,12 +437,13 @@ __device__ __forceinline__ void mask_scan(int *__restrict__ blk, int nblk, int *
     }
 }
 
-__global__ void __launch_bounds__(RS_SEL_BLOCK) k_mask_scan(int *__restrict__ blk, int nblk, int *__restrict__ ndata, int *__restrict__ ndata_out)
+__global__ void __launch_bounds__(RS_SEL_BLOCK) k_mask_scan(int *__restrict__ blk, int ldb, int nblk, int *__restrict__ ndata,
+                                                            int *__restrict__ ndata_out)
 {
-    mask_scan(blk, nblk, ndata, ndata_out);
+    const size_t s = blockIdx.x;
+    mask_scan(blk + s * ldb, nblk, ndata + s, ndata_out ? ndata_out + s : nullptr);
 }
 
-// Writes row rank(p) of the compacted A (columns lda apart) and B for every pixel p with PHI >= 0.
 // The rank of pixel p = blockIdx.x * RS_BLOCK + threadIdx.x among the pixels with PHI >= 0, or -1 when it is not one of them.
 __device__ __forceinline__ int mask_rank(const float *__restrict__ PHI, int npix, const int *__restrict__ blk_off)
 {
@@ -408,32 +460,28 @@ __device__ __forceinline__ int mask_rank(const float *__restrict__ PHI, int npix
     return rank;
 }
 
-template <int NC>
-__global__ void __launch_bounds__(RS_BLOCK) k_mask_scatter(const float *__restrict__ PHI, const float *__restrict__ D, int nrows, int npix,
-                                                           const int *__restrict__ blk_off, float *__restrict__ A, int lda, float *__restrict__ B)
+__global__ void __launch_bounds__(RS_BLOCK) k_mask_scatter(const float *__restrict__ PHI, int npix, const int *__restrict__ blk, int ldb,
+                                                           int *__restrict__ idx, int lda)
 {
-    const int p = blockIdx.x * RS_BLOCK + threadIdx.x;
-    const int rank = mask_rank(PHI, npix, blk_off);
-    if (rank < 0) return;
-    float a[NC];
-    pixel_row<NC>(p % nrows, p / nrows, a);
-#pragma unroll
-    for (int c = 0; c < NC; c++) A[(size_t)c * lda + rank] = a[c];
-    B[rank] = D[p];
+    const size_t s = blockIdx.y;
+    const int rank = mask_rank(PHI + s * npix, npix, blk + s * ldb);
+    if (rank >= 0) idx[s * lda + rank] = blockIdx.x * RS_BLOCK + threadIdx.x;
 }
 
-// dist_out(p) = the error formula on the row of pixel p against D(p), for every pixel.
+// dist_out(s, p) = the error formula on the row of pixel p against D(p) with segment s's winner, for every pixel.
 template <int NC>
 __global__ void __launch_bounds__(RS_BLOCK) k_ransac_dist(const float *__restrict__ D, int nrows, int npix, const float *__restrict__ win,
                                                           float *__restrict__ dist_out)
 {
     const int p = blockIdx.x * RS_BLOCK + threadIdx.x;
     if (p >= npix) return;
+    const size_t seg = blockIdx.y;
+    const float *w = win + seg * RS_SLOT;
     float a[NC], m[NC];
     pixel_row<NC>(p % nrows, p / nrows, a);
 #pragma unroll
-    for (int c = 0; c < NC; c++) m[c] = win[c];
-    dist_out[p] = win[6] != 0.0f ? FLT_MAX : row_error<NC>(a, D[p], m);
+    for (int c = 0; c < NC; c++) m[c] = w[c];
+    dist_out[seg * npix + p] = w[6] != 0.0f ? FLT_MAX : row_error<NC>(a, D[p], m);
 }
 
 } // namespace ransac

@@ -145,6 +145,17 @@ def test_masked_form(pdeip, name):
         PHI, D, order, M_in, iter, seed, _ = rc.masked_case(name)
         A, B = ref.masked_data(PHI, D, order)
         _check(pdeip, A, B, M_in, 0.1, 0.3, iter, r, name + " matrix form", seed=seed)
+    PHI, D, order, M_in, iter, seed, _ = rc.masked_case(name)
+    if iter > 0 and ndata > 0:  # the seed's draws handed over as an explicit list of ranks: the same call
+        seeded = [t[k].cpu().numpy().copy() for k in ("M_out", "dist", "ndata")]
+        sets = torch.from_numpy(ref.sample_sets(seed, iter, t["M_out"].numel() + 1, ndata).astype(np.int32)).cuda()
+        t["M_out"].fill_(7.0)
+        t["dist"].fill_(-2.0)
+        t["ndata"].fill_(-1)
+        dev.surface_fit_masked(t["PHI"], t["D"], order, t["M_in"], 0.1, 0.3, iter, t["M_out"], t["dist"], t["ndata"], seed=seed + 1, sets=sets)
+        torch.cuda.synchronize()
+        for k, want in zip(("M_out", "dist", "ndata"), seeded):
+            assert t[k].cpu().numpy().tobytes() == want.tobytes(), name + " with explicit sets: " + k
 
 
 def test_masked_form_without_optional_outputs(pdeip):

@@ -31,8 +31,7 @@ ROOT = os.path.abspath(os.path.join(os.path.dirname(os.path.abspath(__file__)), 
 SHAPES = [(115, 154), (288, 384)]
 SEGMENTS, ITERATIONS, REF_ITERATIONS = 15, 30, 2
 KERNELS = ("k_seg_sizes_final", "k_seg_sizes", "k_seg_variance_final", "k_seg_variance", "k_seg_data", "k_cv_terms", "k_cv_lines", "k_cv_combine",
-           "k_mask_count", "k_mask_scan", "k_mask_scatter", "k_ransac_fit", "k_ransac_score", "k_ransac_select", "k_ransac_dist",
-           "k_maskb_count", "k_maskb_scan", "k_maskb_scatter", "k_fitb", "k_scoreb", "k_selectb", "k_distb", "k_copy_d2d")
+           "k_mask_count", "k_mask_scan", "k_mask_scatter", "k_ransac_fit", "k_ransac_score", "k_ransac_select", "k_ransac_dist", "k_copy_d2d")
 FIT_KERNELS = KERNELS[KERNELS.index("k_mask_count"):KERNELS.index("k_copy_d2d")]
 FORMS = ("batched", "chained")
 SWITCH = "PDEIP_SEG_FIT_CHAINS"
