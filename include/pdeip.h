@@ -1378,6 +1378,81 @@ int pdeip_tv_pd_dev(void *stream, const float *f, const float *u0 /* or NULL */,
 /* the same without `stream`, on host pointers */
 int pdeip_tv_pd(const float *f, const float *u0, int nrows, int ncols, int frames, const pdeip_tvpd_params *prm, float *u_out);
 
+/* ---- TV-L1 optical flow: primal-dual, warped, coarse to fine (csrc/pdeip_tvl1.hip, csrc/pdeip_drivers.hip) -----------------------------
+ *
+ * This library's own calls (the reference's flow drivers are lagged-diffusivity models solved by SOR or line relaxation): the TV-L1
+ * flow of Zach, Pock and Bischof,  min_{u,v}  TV(u, v) + lambda |rho(u, v)|  with rho the brightness constancy linearised about the
+ * flow of one warp, by the first-order primal-dual iteration of Chambolle and Pock; the Huber norm in place of TV when huber > 0.
+ * No linear solver, no eps.  Planes are column-major float32 [nrows x ncols], i the contiguous row index; x runs along the columns
+ * with flow U, y down the rows with flow V.  The contract, in float32 without contraction, / and sqrt correctly rounded, in exactly
+ * this order; tl = tau lambda and 1 + sigma huber are each formed once on the host in float32 (tests/tvl1_ref.py restates it, and the
+ * device equals it bit for bit).
+ *
+ * Linearisation of one warp about (U0, V0) -- pdeip_tvl1_rc_dev, 1 launch:
+ *   W = frame 1 warped by pdeip_flow_warp_dev;  gx, gy = the Idx, Idy planes of pdeip_fst_derivatives5_dev(I0, W)  (its Idt is not used)
+ *   rc = ((W - I0) - gx U0) - gy V0          NaN wherever the warp left the frame: "no data here"
+ *
+ * The iteration -- pdeip_tvl1_iterate_dev.  State u, v, u_prev, v_prev and the four dual planes pxu, pyu, pxv, pyv.  A call starts from
+ * u = u_prev = U, v = v_prev = V and from the duals in P (four planes of nrows x ncols, contiguous, in the order above), or from zero
+ * duals with P == NULL.  Each of the `iter` iterations:
+ *   ub = (u + u) - u_prev;   vb = (v + v) - v_prev
+ *   gxu[i,j] = ub[i+1,j] - ub[i,j] (0 on the last row);  gyu[i,j] = ub[i,j+1] - ub[i,j] (0 on the last column);  gxv, gyv of vb likewise
+ *   q*  = p* + sigma g*  for each of the four;   huber > 0: each q* = q* / (1 + sigma huber)
+ *   s   = sqrt((qxu qxu + qyu qyu) + (qxv qxv + qyv qyv))      the joint norm of the four
+ *   n   = s > 1 ? s : 1                                        (a NaN norm divides by 1)
+ *   p*' = q* / n
+ *   du  = (pxu'[i,j] - pxu'[i-1,j]) + (pyu'[i,j] - pyu'[i,j-1])   (a missing neighbour: the term is pxu'[i,j] / pyu'[i,j] alone); dv likewise
+ *   a   = u + tau du;   b = v + tau dv
+ *   g2  = gx gx + gy gy;   rho = (rc + gx a) + gy b;   t = tl g2
+ *   c   = rho > t ? -tl : rho < -t ? tl : g2 > 0 ? -rho / g2 : 0
+ *   rc is NaN:  u' = a, v' = b;   otherwise:  u' = a + c gx, v' = b + c gy
+ *   u_prev' = u;  v_prev' = v
+ * Settled here: every comparison with a NaN is false, so a NaN rho or g2 beside a number in rc takes the last two branches in turn (and
+ * u', v' become NaN); a pixel with gx = gy = 0 has c = +0 and u' = a + 0 * 0.  +-Inf in rc is data.  pxu and pxv stay exactly 0 on the
+ * last row, pyu and pyv on the last column, so 1 x N, N x 1 and 1 x 1 planes need no special case.
+ * On return U_out, V_out hold u, v and, with P given, P holds the duals; u_prev, v_prev are not handed on: the next call starts from
+ * u_prev = u again.  iter = 0 copies U, V to U_out, V_out and leaves P alone.  Members of prm: NaN = the default (lambda 15, huber 0, tau
+ * 0.25, sigma 0.5; tau sigma 8 = 1, both exact in binary); iter has none.  rc, gx, gy, U, V are never written; planes may start at any
+ * 4-byte offset.  Kernels: k_tvl1_step does one iteration per launch, each thread recomputing the duals of its north and west
+ * neighbour; k_tvl1_block<T> does T per launch on LDS tiles with a halo of T; both give the same bits.  Environment PDEIP_TVL1_STEPS:
+ * unset or 0 the library's choice, 1 single steps, 2 / 4 blocks of that many.
+ * _dev: device pointers, launches on `stream`, nothing read back, graph-capturable once an eager call has created the workspace
+ * (sixteen planes).  Launches (pdeip_last_launch_count()), a function of iter, T and P == NULL alone, with T = 1 for single steps:
+ *   iter = 0: 2 (the copies);   iter >= 1: L + [P != NULL and L = 1]  with  L = (T > 1 ? iter / T + iter % T : iter)   (the single
+ *   launch of such a call cannot write the planes its neighbours still read, so its duals reach P by a copy)
+ * pdeip_set_mode does not apply.
+ * Refused with PDEIP_ERR_ARG before any HIP call: a NULL plane (P excepted), prm or output; an output that is an input, the other
+ * output or within P; P equal to an input plane; a side < 1; more than 2^31-1 elements; lambda or huber negative or infinite; iter < 0;
+ * tau or sigma not positive and finite; tau sigma 8 > 1 (evaluated in double); an unsupported PDEIP_TVL1_STEPS.
+ * PDEIP_ERR_UNSUPPORTED: more than 65535 columns.
+ *
+ * The level -- `warps` times: W = warp of frame 1 by (U, V); gx, gy; rc; `iter` iterations from (U, V); (U, V) = medfilt2 of both
+ * (pdeip_median3_pair_dev).  The duals are zero at the start of a scale and persist from warp to warp within it.
+ *
+ * pdeip_flow_tvl1 -- the whole driver on host pointers, one resident run: Iin [nrows x ncols x 2], gray, 0..255, is divided by 255; the
+ * pyramid is that of pdeip_flow_nd_llin (scl_factor 0.75, down to a side <= 20, the 5 x 5 Gaussian of sigma 1.25, the coarsest scale
+ * smoothed too); the start is zero; from the coarsest scale on [the level; U (1 / scl_factor) resized bilinearly to the finer scale, no
+ * median there]; the duals are not carried between scales.  The frames go up once and U, V [nrows x ncols] come down once.  A member
+ * of the parameter struct that is <= 0 or NaN keeps the default (lambda 15, huber 0, tau 0.25, sigma 0.5, scl_factor 0.75, warps 3,
+ * iter 20, scales unlimited); NULL: all defaults.  Refused with PDEIP_ERR_ARG before any HIP call: a NULL Iin, U or V; U == V; a side
+ * < 2; more than 2^31-1 elements; an infinite lambda or huber; bad step sizes (as above); scl_factor not below 1. */
+typedef struct {
+    double lambda; /* data weight; NaN = 15 */
+    double huber;  /* 0 = TV, > 0 = Huber-TV; NaN = 0 */
+    int iter;
+    double tau;   /* NaN = default */
+    double sigma; /* NaN = default */
+} pdeip_tvl1_params;
+typedef struct {
+    double lambda, huber, tau, sigma, scl_factor;
+    int warps, iter, scales;
+} pdeip_flow_tvl1_params;
+int pdeip_tvl1_rc_dev(void *stream, const float *I0, const float *W, const float *gx, const float *gy, const float *U0, const float *V0,
+                      int nrows, int ncols, float *rc);
+int pdeip_tvl1_iterate_dev(void *stream, const float *rc, const float *gx, const float *gy, const float *U, const float *V,
+                           float *P /* or NULL */, int nrows, int ncols, const pdeip_tvl1_params *prm, float *U_out, float *V_out);
+int pdeip_flow_tvl1(const float *Iin, int nrows, int ncols, const pdeip_flow_tvl1_params *prm, float *U, float *V);
+
 /* ---- structure-tensor anisotropic diffusion (csrc/pdeip_stensor.hip) --------------------------------------------------------
  * Weickert's edge-enhancing (EED) and coherence-enhancing (CED) diffusion, each semi-implicit step (I - tau A(u^k)) u^{k+1} = u^k
  * one PDEsolver8 solve by pdeip_pde_sor8_dev / pdeip_pde_alr8_dev.  Not in the reference toolbox; tests/stensor_ref.py restates

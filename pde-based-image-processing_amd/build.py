@@ -40,6 +40,7 @@ UNITS = {
     "pdeip_interp.hip": ["pdeip_interp.hpp", "pdeip_bilinear.hpp"],
     "pdeip_edt.hip": ["pdeip_edt.hpp"],
     "pdeip_tvpd.hip": ["pdeip_tvpd.hpp"],
+    "pdeip_tvl1.hip": ["pdeip_tvl1.hpp"],
     "pdeip_stensor.hip": ["pdeip_stensor.hpp", "pdeip_tensor8.hpp", "pdeip_models.hpp", "pdeip_pointwise.hpp"],
 }
 # -ffp-contract=off is part of the parity contract (the reference is FMA-free C).

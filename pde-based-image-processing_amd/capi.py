@@ -210,6 +210,10 @@ SIGNATURES = {
     # primal-dual total variation (csrc/pdeip_tvpd.hip)
     "pdeip_tv_pd_dev": [_P, _P, _P, _I, _I, _I, _P, _P],
     "pdeip_tv_pd": [_P, _P, _I, _I, _I, _P, _P],
+    # TV-L1 optical flow (csrc/pdeip_tvl1.hip, csrc/pdeip_drivers.hip)
+    "pdeip_tvl1_rc_dev": [_P] * 7 + [_I, _I, _P],
+    "pdeip_tvl1_iterate_dev": [_P] * 7 + [_I, _I, _P, _P, _P],
+    "pdeip_flow_tvl1": [_P, _I, _I, _P, _P, _P],
     # structure-tensor anisotropic diffusion (csrc/pdeip_stensor.hip)
     "pdeip_gauss_taps": [ctypes.c_double, _P, _I, ctypes.POINTER(ctypes.c_int)],
     "pdeip_gauss": [_P, _I, _I, _I, ctypes.c_double, _P],

@@ -21,7 +21,7 @@
 
 namespace pdeip {
 
-enum { WS_AUX0 = 0, WS_AUX1, WS_PING, WS_ARENA, WS_CTL, WS_ORDER, WS_ALR, WS_ALR_T, WS_TV, WS_SMALL, WS_MAIL, WS_PACK, WS_DRIVER, WS_LEX, WS_LS, WS_RANSAC, WS_SEG_STAGE, WS_SEG, WS_SEG_RC, WS_CCL, WS_SEEDS, WS_SELECT, WS_GAC, WS_RANSAC_BATCH, WS_FLOWVIZ, WS_CROSSCHECK, WS_INTERP, WS_GAUSS, WS_STENSOR, WS_EDT, WS_TVPD, WS_NSLOT };
+enum { WS_AUX0 = 0, WS_AUX1, WS_PING, WS_ARENA, WS_CTL, WS_ORDER, WS_ALR, WS_ALR_T, WS_TV, WS_SMALL, WS_MAIL, WS_PACK, WS_DRIVER, WS_LEX, WS_LS, WS_RANSAC, WS_SEG_STAGE, WS_SEG, WS_SEG_RC, WS_CCL, WS_SEEDS, WS_SELECT, WS_GAC, WS_RANSAC_BATCH, WS_FLOWVIZ, WS_CROSSCHECK, WS_INTERP, WS_GAUSS, WS_STENSOR, WS_EDT, WS_TVPD, WS_TVL1, WS_NSLOT };
 
 constexpr int MAX_DEVICES = 16;
 
@@ -150,6 +150,11 @@ int sparse_pyramid_dev(hipStream_t s, const float *D, const int *rc, int K, floa
 
 // The refusals of pdeip_tv_inpaint4_dev for a frame and a parameter struct, without a launch (pdeip_inpaint.hip).
 int inpaint_check_params(const char *who, int nrows, int ncols, int frames, const pdeip_inpaint_params *prm);
+
+// TV-L1 flow (pdeip_tvl1.hip): the parameter refusals shared by pdeip_tvl1_iterate_dev and pdeip_flow_tvl1, without a HIP call, and the
+// iteration's workspace sized for planes of up to nrows x ncols (a coarse-to-fine run grows it once, before its first launch).
+int tvl1_check_params(const char *who, double lambda, double huber, int iter, double tau, double sigma);
+int tvl1_reserve(int nrows, int ncols);
 
 // Makes group[0] (or `device`) the current HIP device; reads the environment knobs on first use.
 int use_device();

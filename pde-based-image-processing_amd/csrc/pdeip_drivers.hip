@@ -28,7 +28,7 @@
 //   llin_driver                     the scale loop of pdeip_flow_nd_llin, pdeip_flow_ad_llin and pdeip_disp_nd_llin, over one or two fields
 //   enter()                         what every entry point refuses before it touches the device, and in which order
 // and the drivers themselves are what is left: their levels (flow_level, flow_ad_level, disp_level, sym_level, Fas), the four
-// scale loops that are not the late-linearisation one (disp_sym, flow_hs, fas_fmg, tv_run) and the entry points.
+// scale loops that are not the late-linearisation one (disp_sym, flow_hs, flow_tvl1, fas_fmg, tv_run) and the entry points.
 #include "pdeip_ctx.hpp"
 
 #include <cmath>
@@ -753,6 +753,59 @@ void flow_hs(Run &R, const float *Iin, int nrows, int ncols, int C, const Params
     download(R, {{U_out, U}, {V_out, V}}, n);
 }
 
+// TV-L1 flow (this library's own driver; include/pdeip.h has the contract, drivers.py FlowTVL1 / flow_level.py FlowTvl1Level are the
+// statement the tests compare with): the late-linearisation drivers' pyramid and scale loop around a level of `warps` x [warp,
+// derivatives, rc, `iter` primal-dual iterations, median].  The duals start a scale at zero and persist from warp to warp within it.
+struct Tvl1Params {
+    double lambda, huber, tau, sigma, scl_factor;
+    int warps, iter, scales;
+};
+void tvl1_level(Run &R, const Tvl1Params &p, const Level &lv, Fields &F)
+{
+    const int nr = lv.nr, nc = lv.nc;
+    const size_t m = R.mark();
+    float *W = R.planes(nr, nc), *gt = R.planes(nr, nc), *gx = R.planes(nr, nc), *gy = R.planes(nr, nc), *rc = R.planes(nr, nc);
+    float *P = R.planes(nr, nc, 4), *iu = R.planes(nr, nc), *iv = R.planes(nr, nc);
+    const pdeip_tvl1_params prm{p.lambda, p.huber, p.iter, p.tau, p.sigma};
+    DOHIP(R, hipMemsetAsync(P, 0, 4 * lv.n() * sizeof(float), R.s));
+    for (int w = 0; w < p.warps; w++) {
+        DO(R, pdeip_flow_warp_dev(R.s, F.f[0], F.f[1], lv.I1, 1, nullptr, 0, nr, nc, W, nullptr));
+        DO(R, pdeip_fst_derivatives5_dev(R.s, lv.I0, W, nr, nc, 1, gt, gx, gy)); // Idt has the reference's sign and scale: not used
+        DO(R, pdeip_tvl1_rc_dev(R.s, lv.I0, W, gx, gy, F.f[0], F.f[1], nr, nc, rc));
+        DO(R, pdeip_tvl1_iterate_dev(R.s, rc, gx, gy, F.f[0], F.f[1], P, nr, nc, &prm, iu, iv));
+        DO(R, pdeip_median3_pair_dev(R.s, iu, nullptr, iv, nullptr, nr, nc, F.alt[0], F.alt[1]));
+        std::swap(F.f[0], F.alt[0]);
+        std::swap(F.f[1], F.alt[1]);
+    }
+    R.release(m);
+}
+void flow_tvl1(Run &R, const float *Iin, int nrows, int ncols, const Tvl1Params &p, float *U_out, float *V_out)
+{
+    float *fr = upload_frames(R, Iin, nullptr, nrows, ncols, 1, true);
+    const std::vector<Level> L = build_pyramid(R, 2, fr, fr + (size_t)nrows * ncols, nrows, ncols, 1, {p.scl_factor, p.scales, 20, 20, true, 5, 1.25, false});
+    const int last = (int)L.size() - 1;
+    Fields F;
+    F.nf = 2;
+    for (int k = 0; k < 2; k++) F.f[k] = zero_plane(R, L[last].nr, L[last].nc);
+    for (int k = 0; k < 2; k++) F.alt[k] = R.planes(L[last].nr, L[last].nc);
+    DO(R, tvl1_reserve(nrows, ncols)); // the iteration's workspace grows once, before the first launch that uses it
+    const float inv = (float)(1.0 / p.scl_factor);
+    for (int s = last; s >= 0; s--) {
+        const size_t m = R.mark();
+        tvl1_level(R, p, L[s], F);
+        if (s > 0) { // U = imresize(U .* (1/scl_factor), size of the finer scale, 'triangle'), as llin_driver has it
+            const Level &f = L[s - 1];
+            for (int k = 0; k < 2; k++) scale(R, F.alt[k], F.f[k], L[s].n(), inv, false);
+            R.release(m);
+            const Fields coarse = F;
+            for (int k = 0; k < 2; k++) F.f[k] = R.planes(f.nr, f.nc);
+            for (int k = 0; k < 2; k++) F.alt[k] = R.planes(f.nr, f.nc);
+            for (int k = 0; k < 2; k++) DO(R, pdeip_pyr_resize_dev(R.s, coarse.alt[k], L[s].nr, L[s].nc, 1, f.nr, f.nc, 0, F.f[k]));
+        }
+    }
+    download(R, {{U_out, F.f[0]}, {V_out, F.f[1]}}, L[0].n());
+}
+
 // FlowEminNDFASFMG_elin_2D_v10.m (runme.m:90): FAS full-multigrid flow with early linearisation.  Image pyramid by halving
 // (:104-120), per-scale derivative planes and constants (:125-153), per scale, coarse to fine (:161-183), one FAS V- or W-cycle
 // (FAS_CYCLE, :193-273) whose smoother (:367-464) is firstLoop x [robust data weights + OPdiffWeights, Oflow_sor_elin4_2d];
@@ -1018,6 +1071,25 @@ extern "C" int pdeip_flow_hs_elin(const float *Iin, int nrows, int ncols, int ch
     p.scales = ALL_SCALES;
     RC(enter(who, {ARG(Iin), ARG(U), ARG(V)}, nrows, ncols, channels, nullptr, p.solver, &p.scl_factor));
     return play(who, [&](Run &R) { flow_hs(R, Iin, nrows, ncols, channels, p, U, V); });
+}
+
+extern "C" int pdeip_flow_tvl1(const float *Iin, int nrows, int ncols, const pdeip_flow_tvl1_params *prm, float *U, float *V)
+{
+    const char *who = "pdeip_flow_tvl1";
+    Tvl1Params p{15.0, 0.0, 0.25, 0.5, 0.75, 3, 20, ALL_SCALES};
+    if (prm != nullptr) {
+        p.lambda = or_default(prm->lambda, p.lambda), p.huber = or_default(prm->huber, p.huber), p.tau = or_default(prm->tau, p.tau);
+        p.sigma = or_default(prm->sigma, p.sigma), p.scl_factor = or_default(prm->scl_factor, p.scl_factor);
+        p.warps = or_default(prm->warps, p.warps), p.iter = or_default(prm->iter, p.iter), p.scales = or_default(prm->scales, p.scales);
+    }
+    NONNULL(who, Iin); NONNULL(who, U); NONNULL(who, V);
+    if (U == V) return set_err(PDEIP_ERR_ARG, "%s: U is V", who);
+    if (nrows < 2 || ncols < 2) return set_err(PDEIP_ERR_ARG, "%s: the frames must be at least 2x2 (got %dx%d)", who, nrows, ncols);
+    if ((long long)nrows * ncols * 2 > 0x7fffffffLL) return set_err(PDEIP_ERR_ARG, "%s: more than 2^31-1 elements", who);
+    RC(tvl1_check_params(who, p.lambda, p.huber, p.iter, p.tau, p.sigma));
+    if (!(p.scl_factor < 1.0)) return set_err(PDEIP_ERR_ARG, "%s: scl_factor must be below 1", who);
+    if (ncols > 65535) return set_err(PDEIP_ERR_UNSUPPORTED, "%s: more than 65535 columns (got %d): the launch geometry", who, ncols);
+    return play(who, [&](Run &R) { flow_tvl1(R, Iin, nrows, ncols, p, U, V); });
 }
 
 extern "C" int pdeip_flow_fas_fmg_elin(const float *Iin, int nrows, int ncols, int channels, const pdeip_fas_params *prm, float *U, float *V)

@@ -487,10 +487,10 @@ def median3(A, B, out):
 
 
 def median3_pair(A0, B0, out0, A1, B1, out1):
-    """out0 = medfilt2(A0 + B0), out1 = medfilt2(A1 + B1) in one launch."""
-    _chk(A0, B0, out0, A1, B1, out1)
+    """out0 = medfilt2(A0 + B0), out1 = medfilt2(A1 + B1) in one launch; B0 / B1 may be None (out = medfilt2(A))."""
+    _chk(*(t for t in (A0, B0, out0, A1, B1, out1) if t is not None))
     nrows, ncols, _ = _dims(A0)
-    capi.call("pdeip_median3_pair_dev", _stream(), *_p(A0, B0, A1, B1), nrows, ncols, *_p(out0, out1))
+    capi.call("pdeip_median3_pair_dev", _stream(), A0.data_ptr(), _ptr(B0), A1.data_ptr(), _ptr(B1), nrows, ncols, *_p(out0, out1))
 
 
 def nanmedfilt2(A, out=None):
@@ -1292,3 +1292,55 @@ def tv_pd(f, model, lam, iter, huber=0, u0=None, tau=None, sigma=None, out=None)
     out = _out_plane(f, out, True, "tv_pd: out")
     capi.call("pdeip_tv_pd_dev", _stream(), f.data_ptr(), _ptr(u0), nrows, ncols, F, ctypes.addressof(prm), out.data_ptr())
     return out
+
+
+# ---- TV-L1 optical flow: the linearisation's rc and the primal-dual iteration (csrc/pdeip_tvl1.hip) ----
+class Tvl1Params(ctypes.Structure):
+    """pdeip_tvl1_params: the data weight lambda (NaN = 15), huber (0 = TV; NaN = 0), iter, tau and sigma (NaN = 0.25 and 0.5)."""
+    _fields_ = [("lambda_", ctypes.c_double), ("huber", ctypes.c_double), ("iter", ctypes.c_int), ("tau", ctypes.c_double), ("sigma", ctypes.c_double)]
+
+    @classmethod
+    def make(cls, lam=None, iter=20, huber=None, tau=None, sigma=None):
+        nan = float("nan")
+        d = lambda v: nan if v is None else float(v)
+        return cls(d(lam), d(huber), int(iter), d(tau), d(sigma))
+
+
+class FlowTvl1Params(ctypes.Structure):
+    """pdeip_flow_tvl1_params: a member that is <= 0 or NaN keeps the driver's default."""
+    _fields_ = [("lambda_", ctypes.c_double), ("huber", ctypes.c_double), ("tau", ctypes.c_double), ("sigma", ctypes.c_double),
+                ("scl_factor", ctypes.c_double), ("warps", ctypes.c_int), ("iter", ctypes.c_int), ("scales", ctypes.c_int)]
+
+
+def tvl1_rc(I0, W, gx, gy, U0, V0, out=None):
+    """rc = ((W - I0) - gx U0) - gy V0 of one warp's linearisation (pdeip_tvl1_rc_dev): planes [ncols, nrows]; NaN in W (the warp left
+    the frame) makes rc NaN, "no data here".  Returns out."""
+    _chk(I0, W, gx, gy, U0, V0)
+    nrows, ncols, _ = _dims(U0)
+    for t in (I0, W, gx, gy, V0):
+        if t.numel() != U0.numel():
+            raise capi.PdeipError(capi.PDEIP_ERR_ARG, "tvl1_rc: the planes must have one size")
+    out = _out_plane(U0, out, True, "tvl1_rc: out")
+    capi.call("pdeip_tvl1_rc_dev", _stream(), *_p(I0, W, gx, gy, U0, V0), nrows, ncols, out.data_ptr())
+    return out
+
+
+def tvl1_iterate(rc, gx, gy, U, V, lam=None, iter=20, huber=None, P=None, tau=None, sigma=None, out=None):
+    """`iter` primal-dual iterations of TV-L1 flow on one linearisation (pdeip_tvl1_iterate_dev) from u = u_prev = U, v = v_prev = V.
+    P [4, ncols, nrows]: the duals pxu, pyu, pxv, pyv, read and updated in place; None: zero duals, the result discarded.  lam, huber,
+    tau, sigma: None = 15, 0, 0.25 and 0.5.  rc, gx, gy, U, V are not modified; out = (U_out, V_out) must be none of them.  Returns
+    (U_out, V_out).  Nothing is read back."""
+    _chk(rc, gx, gy, U, V)
+    nrows, ncols, _ = _dims(U)
+    for t in (rc, gx, gy, V):
+        if t.numel() != U.numel():
+            raise capi.PdeipError(capi.PDEIP_ERR_ARG, "tvl1_iterate: the planes must have one size")
+    if P is not None:
+        _chk(P)
+        if P.numel() != 4 * U.numel():
+            raise capi.PdeipError(capi.PDEIP_ERR_ARG, "tvl1_iterate: P is %s, not four planes of %s" % (tuple(P.shape), tuple(U.shape)))
+    Uo, Vo = (None, None) if out is None else out
+    Uo, Vo = _out_plane(U, Uo, True, "tvl1_iterate: U_out"), _out_plane(V, Vo, True, "tvl1_iterate: V_out")
+    prm = Tvl1Params.make(lam, iter, huber, tau, sigma)
+    capi.call("pdeip_tvl1_iterate_dev", _stream(), *_p(rc, gx, gy, U, V), _ptr(P), nrows, ncols, ctypes.addressof(prm), *_p(Uo, Vo))
+    return Uo, Vo

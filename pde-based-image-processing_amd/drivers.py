@@ -22,6 +22,7 @@ capi.MODE_RED_BLACK the parallel one).
     gaussian / Diffusion8       this library's own: smoothing at a chosen scale; structure-tensor diffusion, EED and CED (pdeip_diffusion8)
     bwdist / signed_distance / nearest_fill   this library's own: exact Euclidean distance transform (pdeip_bwdist, pdeip_signed_distance, pdeip_nearest_fill)
     TVdenoisePD                 this library's own: primal-dual total variation, TV-L1 / ROF / Huber-TV (pdeip_tv_pd)
+    FlowTVL1                    this library's own: TV-L1 optical flow, primal-dual, warped, coarse to fine (pdeip_flow_tvl1)
 
 `Us=`, `Vs=` (param.Us / param.Vs: spatial a-priori fields, double, NaN = no constraint) and `scales=` (param.scales) are taken
 by the late-linearisation flow drivers and the disparity driver as the reference's drivers take them.
@@ -1067,12 +1068,17 @@ def flow_interpolate(I0, I1, U, V, Ub=None, Vb=None, t=0.5, return_flow=False, r
     return out[0] if len(out) == 1 else out
 
 
-def interpolate_frames(Iin, channels, t=(0.5,), mode=capi.MODE_EXACT_ORDER, fstTerm="rgb", sndTerm="none", return_flows=False, **param):
+def interpolate_frames(Iin, channels, t=(0.5,), mode=capi.MODE_EXACT_ORDER, fstTerm="rgb", sndTerm="none", return_flows=False, flow="llin", **param):
     """In-between frames of Iin = cat(3, frame0, frame1): FlowEminND_llin_2D_v10's level loop forward and with the frames swapped,
     then the chain of flow_interpolate for every t, all on the device with one download at the end.  param: the flow driver's
     parameters; the chain's go in interp=dict(...), fill_with="nearest" and its max_dist among them.  Returns the list of frames [rows, cols(, channels)], one per t (values on Iin's
-    scale); with return_flows also the forward and the backward flow as [rows, cols, 2] arrays."""
+    scale); with return_flows also the forward and the backward flow as [rows, cols, 2] arrays.
+    flow="tvl1": both flows by FlowTVL1's level loop instead (param: its parameters; a colour pair's flows from its gray pair)."""
     who = "interpolate_frames"
+    if flow not in ("llin", "tvl1"):
+        raise ValueError("%s: flow must be 'llin' or 'tvl1' (got %r)" % (who, flow))
+    if flow == "tvl1":
+        return _interpolate_frames_tvl1(who, Iin, channels, t, mode, return_flows, dict(param))
     param = dict(param)
     interp = dict(param.pop("interp", None) or {})
     interp.pop("mode", None)
@@ -1085,6 +1091,28 @@ def interpolate_frames(Iin, channels, t=(0.5,), mode=capi.MODE_EXACT_ORDER, fstT
     f0, f1 = dev.div_scalar(I0, 255.0), dev.div_scalar(I1, 255.0)
     Uf, Vf = _flow_llin_planes(fl.FlowLlinLevel, f0, f1, fstTerm, sndTerm, p, mode, scales=scales)
     Ub, Vb = _flow_llin_planes(fl.FlowLlinLevel, f1, f0, fstTerm, sndTerm, p, mode, scales=scales)
+    Uf, Vf, Ub, Vb = (x.contiguous() for x in (Uf, Vf, Ub, Vb))
+    frames = [dev.flow_interpolate(I0, I1, Uf, Vf, Ub, Vb, t=x, flow=False, source=False, mode=mode, **prm_kw)[0] for x in times]
+    dev.sync_check()
+    out = [dev.to_matlab(f) for f in frames]
+    if channels == 1:
+        out = [f[:, :, 0] for f in out]
+    if return_flows:
+        both = lambda a, b: np.stack([dev.to_matlab(a), dev.to_matlab(b)], axis=2)
+        return out, both(Uf, Vf), both(Ub, Vb)
+    return out
+
+
+def _interpolate_frames_tvl1(who, Iin, channels, t, mode, return_flows, param):
+    interp = dict(param.pop("interp", None) or {})
+    interp.pop("mode", None)
+    _, prm_kw = _interp_param(who, interp)
+    times = [_time(who, x) for x in (t if np.ndim(t) else (t,))]
+    p = _tvl1_param(who, param)
+    I0, I1 = _frames(Iin, channels)
+    g0, g1 = _tvl1_frames(_tvl1_gray_pair(who, Iin, channels))
+    Uf, Vf = _flow_tvl1_planes(g0, g1, p)
+    Ub, Vb = _flow_tvl1_planes(g1, g0, p)
     Uf, Vf, Ub, Vb = (x.contiguous() for x in (Uf, Vf, Ub, Vb))
     frames = [dev.flow_interpolate(I0, I1, Uf, Vf, Ub, Vb, t=x, flow=False, source=False, mode=mode, **prm_kw)[0] for x in times]
     dev.sync_check()
@@ -1178,3 +1206,79 @@ def capi_TVdenoisePD(I, model="l1", lam=0.8, iter=300, huber=0.0, u0=None, tau=N
     out = np.empty(f.shape, np.float32, order="F")
     capi.call("pdeip_tv_pd", f.ctypes.data, _ptr(s), rows, cols, F, ctypes.addressof(prm), out.ctypes.data)
     return out
+
+
+# ---- TV-L1 optical flow: primal-dual, warped, coarse to fine (include/pdeip.h; this library's own driver) ----
+TVL1_DEFAULTS = dict(lam=15.0, warps=3, iter=20, huber=0.0, scl_factor=0.75, scales=None, tau=None, sigma=None)
+
+
+def _tvl1_param(who, param):
+    unknown = sorted(set(param) - set(TVL1_DEFAULTS))
+    if unknown:
+        raise ValueError("%s: unknown parameter %s (of %s)" % (who, ", ".join(unknown), ", ".join(sorted(TVL1_DEFAULTS))))
+    p = dict(TVL1_DEFAULTS, **param)
+    if not int(p["warps"]) > 0 or not int(p["iter"]) > 0 or not float(p["lam"]) > 0:
+        raise ValueError("%s: lam, warps and iter must be positive" % who)
+    return p
+
+
+def _tvl1_gray_pair(who, Iin, channels):
+    """Both frames of Iin = cat(3, frame0, frame1), 0..255, as resident gray planes [1, ncols, nrows] ./ 255; a colour pair's gray value
+    is ((R + G) + B) / 3 in float32, formed on the host."""
+    I = np.asarray(Iin, dtype=np.float32)
+    if channels not in (1, 3) or I.ndim != 3 or I.shape[2] != 2 * channels:
+        raise ValueError("%s: Iin must be [rows, cols, 2 * channels] with channels 1 or 3 (got %s, channels %r)" % (who, I.shape, channels))
+    if I.shape[0] < 2 or I.shape[1] < 2:
+        raise ValueError("%s: the frames must be at least 2x2 (got %s)" % (who, I.shape[:2]))
+    if channels == 3:
+        three = np.float32(3.0)
+        I = np.stack([((I[:, :, 0] + I[:, :, 1]) + I[:, :, 2]) / three, ((I[:, :, 3] + I[:, :, 4]) + I[:, :, 5]) / three], axis=2)
+    return I
+
+
+def _tvl1_frames(gray):
+    I0, I1 = _frames(gray, 1)
+    return dev.div_scalar(I0, 255.0), dev.div_scalar(I1, 255.0)
+
+
+def _flow_tvl1_planes(f0, f1, p):
+    """The level loop of FlowTVL1 on resident gray frames f0, f1 [1, ncols, nrows] (already ./255): the flow as two resident planes."""
+    P0, P1 = pyramid.build_dev(f0, f1, p["scl_factor"], 20, max_scales=p["scales"])
+    level = fl.FlowTvl1Level(p)
+    U = _zeros_like_plane(P0[-1])
+    V = torch.zeros_like(U)
+    for scl in range(len(P0) - 1, -1, -1):
+        U, V = level.run(P0[scl], P1[scl], U, V)
+        if scl > 0:
+            cols, rows = P0[scl - 1].shape[-2:]
+            U, V = _up(U, 1.0 / p["scl_factor"], rows, cols), _up(V, 1.0 / p["scl_factor"], rows, cols)
+    return U, V
+
+
+def FlowTVL1(Iin, channels=1, **param):
+    """[U V] = TV-L1 optical flow of Iin = cat(3, frame0, frame1), values 0..255: Zach, Pock and Bischof's model by Chambolle and Pock's
+    primal-dual iteration, warped and coarse to fine on the late-linearisation drivers' pyramid, resident on the device
+    (pyramid.build_dev and flow_level.FlowTvl1Level).  param: lam (15), warps (3) per scale, iter (20) per warp, huber (0 = TV),
+    scl_factor (0.75), scales (all), tau, sigma (0.25, 0.5).  channels = 3: the flow of the gray pair ((R + G) + B) / 3.  No linear
+    solver and no ordering: `mode` does not apply.  Returns U (along the columns) and V (down the rows), single [rows, cols]."""
+    who = "FlowTVL1"
+    p = _tvl1_param(who, dict(param))
+    U, V = _flow_tvl1_planes(*_tvl1_frames(_tvl1_gray_pair(who, Iin, channels)), p)
+    dev.sync_check()
+    return dev.to_matlab(U), dev.to_matlab(V)
+
+
+def capi_FlowTVL1(Iin, channels=1, **param):
+    """pdeip_flow_tvl1 on MATLAB-shaped numpy arrays: FlowTVL1 through the host entry point, one resident run, same bits.  The C-ABI
+    takes the gray pair; a colour pair's is formed here as in FlowTVL1."""
+    who = "capi_FlowTVL1"
+    p = _tvl1_param(who, dict(param))
+    g = np.asfortranarray(_tvl1_gray_pair(who, Iin, channels), dtype=np.float32)
+    rows, cols = g.shape[:2]
+    nan = float("nan")
+    d = lambda v: nan if v is None else float(v)
+    prm = dev.FlowTvl1Params(float(p["lam"]), float(p["huber"]), d(p["tau"]), d(p["sigma"]), float(p["scl_factor"]), int(p["warps"]), int(p["iter"]),
+                             0 if p["scales"] is None else int(p["scales"]))
+    U, V = np.empty((rows, cols), np.float32, order="F"), np.empty((rows, cols), np.float32, order="F")
+    capi.call("pdeip_flow_tvl1", g.ctypes.data, rows, cols, ctypes.addressof(prm), U.ctypes.data, V.ctypes.data)
+    return U, V

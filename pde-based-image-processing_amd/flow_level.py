@@ -62,6 +62,36 @@ class FlowLlinLevel:
         return U, V
 
 
+class FlowTvl1Level:
+    """One scale of TV-L1 flow (include/pdeip.h; the twin of tvl1_level in csrc/pdeip_drivers.hip): warps x [warp, derivatives, rc,
+    `iter` primal-dual iterations, median].  The duals start at zero and persist from warp to warp.  No solver, no ordering.
+    param: lam, warps, iter, huber, tau, sigma (None: the library's defaults)."""
+
+    def __init__(self, param):
+        self.p = dict(param)
+
+    def run(self, I0, I1, U, V):
+        """I0, I1: [1, ncols, nrows] or [ncols, nrows] gray frames; U, V: [ncols, nrows] flow entering the level.  Returns the flow
+        leaving it (new tensors)."""
+        p = self.p
+        new = lambda like: torch.empty_like(like)
+        I0, I1 = I0.reshape((1,) + tuple(U.shape)), I1.reshape((1,) + tuple(U.shape))
+        W, gt, gx, gy = new(I1), new(I1), new(I1), new(I1)
+        rc, iu, iv = new(U), new(U), new(U)
+        P = torch.zeros((4,) + tuple(U.shape), dtype=U.dtype, device=U.device)
+        U, V = U.clone(), V.clone()
+        Un, Vn = new(U), new(U)
+        for _ in range(int(p.get("warps", 3))):
+            dev.flow_warp(U, V, I1, W)
+            dev.fst_derivatives5(I0, W, gt, gx, gy)      # Idt has the reference's sign and scale: not used
+            dev.tvl1_rc(I0, W, gx, gy, U, V, out=rc)
+            dev.tvl1_iterate(rc, gx, gy, U, V, p.get("lam"), int(p.get("iter", 20)), p.get("huber"), P, p.get("tau"), p.get("sigma"), out=(iu, iv))
+            dev.median3_pair(iu, None, Un, iv, None, Vn)
+            U, Un = Un, U
+            V, Vn = Vn, V
+        return U, V
+
+
 class FlowAdLevel:
     """The anisotropic-diffusion twin (matlab/optical_flow/FlowEminAD_llin_2D_v10.m:198-366): eight ADdiffWeights from
     the image (`diffusion` 'image', once per level) or from U+dU+V+dV ('flow', every inner iteration), and
